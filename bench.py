@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: genotype-dosage accumulations/s on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and
+prints its line.  --full adds everything else that is measured or checked after the headline: the CPU baseline,
+the oracle's check of the scores, the secondary legs (N = 1) and the strong-scaling legs (N > 1).
 
 Workload (BASELINE.json configs[2], the configuration the north-star metric is quoted on):
 synthetic 1 000 000-variant PRS on a 500 000-sample bit-packed GT matrix (125 GB of 2-bit codes)
@@ -95,7 +99,21 @@ def parse_args():
     ap.add_argument("--seed", type=int, default=20250103)
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="--gpus N without a launcher: seconds after which all ranks are killed (exit status 124)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the CPU baseline, the oracle's check of the scores, the secondary legs "
+                         "(N = 1) and the strong-scaling legs (N > 1), the full object written to --full-out; a plain "
+                         "run times the headline steps and prints its line, nothing else (--full-sweeps implies --full)")
+    ap.add_argument("--require-all-legs", action="store_true",
+                    help="--full: a secondary leg with a parity check that the time budget skipped fails the run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): "
+                         "scores (the samples' scores; N > 1 weak: the gathered scores x samples matrix) and nloci")
+    args = ap.parse_args()
+    if args.full_sweeps:
+        args.full = True
+    if args.dump_outputs and args.steps + args.warmup < 1:
+        ap.error("--dump-outputs needs at least one step")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -964,6 +982,27 @@ def config4_e2e(tmpdir, n=500_000):
 
 
 # ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, so that two builds can be compared output for output
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """arrays: {name: array} -> path/<name>.npy in float64.  Past DUMP_LIMIT bytes in all, every array larger than a
+    MiB is cut to the same fixed, seeded sample of its flat elements (sorted), their positions beside it as
+    path/<name>_index.npy; the inputs are seeded, so the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT and a.nbytes > (1 << 20):
+            keep = max(1, int(a.size * (DUMP_LIMIT // 2 - (1 << 20)) / total))   # (sample + index: 16 bytes each)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+# ------------------------------------------------------------------------------------------------
 # output: the driver parses the LAST stdout line; round 4's 20 KB line (every secondary object inline) was not parsed.
 # The full object goes to a side file and to stderr, the last stdout line is the compact one.
 LINE_LIMIT = 4096
@@ -1058,7 +1097,11 @@ PARITY_LEGS = ("given_tallies", "layout_sweep", "size_sweep", "config5_ds", "con
 
 
 def emit(out, full_path):
-    """full object -> side file (+ stderr); compact object -> the last stdout line"""
+    """full object -> side file (+ stderr); compact object -> the last stdout line.  full_path None (a plain run, no
+    --full): the line alone"""
+    if full_path is None:
+        print(json.dumps(compact_line(out)), flush=True)
+        return
     where = None
     try:
         os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
@@ -1197,6 +1240,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        # (before any --full leg: given_tallies rewrites d_scores)
+        scores = step.matrix if (world > 1 and not strong) else d_scores
+        dump_outputs(args.dump_outputs, {"scores": scores.detach().cpu().numpy(), "nloci": [nloci]}, args.seed)
+
     failed = []   # secondary measurements that raised (rank 0): the line is printed, the exit status is 1
     out = None
     if rank == 0:
@@ -1266,12 +1314,13 @@ def main():
                                                "params": prof.n_params / steps,
                                                "accumulate": prof.n_accumulate / steps,
                                                "fused": prof.n_fused / steps}},
+            "seconds": {"to_headline": t_headline - T_START},
         }
     # N > 1: the two strong-scaling curves of the north star, by all ranks, in this order on every rank.  The headline
     # line exists already: if a leg hangs (a collective some rank never reaches), a watchdog prints the line without the
     # legs and ends the process instead of losing the measurement to the caller's timeout.
     multi_legs = None
-    if world > 1 and not args.no_multi_legs and not strong and not is_ds and resident:
+    if world > 1 and args.full and not args.no_multi_legs and not strong and not is_ds and resident:
         import threading
 
         def give_up():
@@ -1299,7 +1348,7 @@ def main():
         watchdog.cancel()
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             t_leg = time.perf_counter()
             if not is_ds:
                 out["cpu_baseline"] = cpu_baseline(n, eaf, miss, args.seed, args.cpu_rows)
@@ -1312,7 +1361,7 @@ def main():
                 out["score_delta_vs_reference"] = score_delta(
                     stats, got, nl, args.format, beta, eaf, args.seed, n, m, t_het, t_hom, t_miss, geometry)
             out["seconds"] = {"to_headline": t_headline - T_START, "cpu_baseline_and_check": time.perf_counter() - t_leg}
-        if world == 1 and not args.no_extras and not is_ds and resident:
+        if world == 1 and args.full and not args.no_extras and not is_ds and resident:
             import tempfile
             import threading
             secondary = {}
@@ -1407,7 +1456,7 @@ def main():
         bad = parity_failures(out)
         if bad:
             out["parity_failures"] = bad
-        emit(out, args.full_out)
+        emit(out, args.full_out if args.full else None)
         failed += ["parity:" + p for p in bad]
     if world > 1:
         dist.barrier()

@@ -23,8 +23,10 @@ def test_cover_columns_touch_every_slice():
 def test_bench_spawns_its_ranks_without_a_launcher():
     """`python bench.py --gpus 2` under plain python (no torch.distributed.run): the parent starts two rank
     processes with RANK / WORLD_SIZE / MASTER_* set and passes their exit code on.  There is no GPU here, so
-    each rank stops with the "needs an MI355X" message -- which proves they were started as ranks."""
+    each rank stops with the "needs an MI355X" message -- which proves they were started as ranks.  (On a host
+    with GPUs the ranks are shown none: the test is of the launcher, never a full-size run.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
                         "--warmup", "0"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
@@ -69,7 +71,7 @@ def _rehearse(world, extra, expect_rc=0, full=None):
 
 def test_bench_two_ranks_weak_scaling_rehearsal():
     full = {}
-    d = _rehearse(2, [], full=full)
+    d = _rehearse(2, ["--full"], full=full)
     assert d["rehearsal"] and d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["scaling"] == "weak"
     assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
     assert d["config"]["parallelism"].startswith("score-sharded x2") and d["config"]["nloci"] == 640
@@ -102,7 +104,7 @@ def test_bench_eight_ranks_weak_scaling_rehearsal():
     all-gather of eight score rows, both strong-scaling legs, the compact line -- runs here over gloo.  The line must stay
     under 4 KiB with `multi_gpu` summarised, and report the eight ranks it really had."""
     full = {}
-    d = _rehearse(8, [], full=full)
+    d = _rehearse(8, ["--full"], full=full)
     assert d["rehearsal"] and d["n_gpus"] == 8 and d["rccl_ranks"] == 8 and d["scaling"] == "weak"
     assert d["config"]["parallelism"].startswith("score-sharded x8") and d["config"]["nloci"] == 640
     legs = d["multi_gpu"]
@@ -124,7 +126,7 @@ def test_bench_eight_ranks_strong_scaling_rehearsal():
 def test_bench_legs_watchdog_keeps_the_headline_line():
     """N > 1: if the strong-scaling legs do not finish in time (a collective some rank never reaches), rank 0 still
     prints the headline line -- without the legs -- and ends with status 3 (the other ranks: non-zero)"""
-    d = _rehearse(2, ["--multi-legs-timeout", "0"], expect_rc=3)
+    d = _rehearse(2, ["--full", "--multi-legs-timeout", "0"], expect_rc=3)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "weak"
     assert "did not finish" in d["multi_gpu"]["error"]
 
@@ -157,7 +159,46 @@ def test_compact_line_stays_under_4k_whatever_the_legs_return():
 
 def test_bench_one_rank_rehearsal_has_roofline_and_full_object():
     full = {}
-    d = _rehearse(1, [], full=full)
+    d = _rehearse(1, ["--full"], full=full)
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and "multi_gpu" not in d
     assert d["roofline"]["achieved"] > 0 and d["config"]["workload"]
     assert full["roofline"]["launches_per_step"]["fused"] > 0   # (the fake library reports one launch, whatever the steps)
+
+
+def test_bench_plain_run_times_the_headline_only():
+    """without --full a run sets up, warms up, times its steps and prints the line: no CPU baseline, no oracle check,
+    no secondary or strong-scaling legs, no full object"""
+    for world in (1, 2):
+        d = _rehearse(world, [])
+        assert d["n_gpus"] == world and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype", "roofline"):
+            assert k in d, k
+        for k in ("cpu_baseline", "score_delta_vs_reference", "secondary_summary", "multi_gpu", "full_object"):
+            assert k not in d, k
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's scores and nloci as float64 .npy files (the fake library scores every
+    sample of rank r as r + 1; N > 1 weak: the gathered scores x samples matrix)"""
+    one, two = str(tmp_path / "one"), str(tmp_path / "two")
+    _rehearse(1, ["--dump-outputs", one])
+    s, nl = np.load(os.path.join(one, "scores.npy")), np.load(os.path.join(one, "nloci.npy"))
+    assert s.dtype == np.float64 and s.shape == (4000,) and np.all(s == 1.0)
+    assert nl.dtype == np.float64 and nl.tolist() == [640.0]
+    _rehearse(2, ["--dump-outputs", two])
+    s = np.load(os.path.join(two, "scores.npy"))
+    assert s.dtype == np.float64 and s.shape == (2, 4000) and np.all(s[0] == 1.0) and np.all(s[1] == 2.0)
+
+
+def test_dump_outputs_keeps_to_its_limit(tmp_path):
+    """past 64 MiB in all the large arrays are cut to a fixed seeded sample, positions beside them"""
+    import bench
+    big = np.arange(12 << 20, dtype=np.float64)               # 96 MiB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"scores": big, "nloci": [7]})
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["nloci.npy", "scores.npy", "scores_index.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= bench.DUMP_LIMIT
+    s, i = np.load(str(tmp_path / "a" / "scores.npy")), np.load(str(tmp_path / "a" / "scores_index.npy"))
+    assert s.dtype == i.dtype == np.float64 and np.array_equal(s, i) and np.all(np.diff(i) > 0)
+    assert np.array_equal(s, np.load(str(tmp_path / "b" / "scores.npy")))
