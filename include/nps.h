@@ -332,7 +332,13 @@ int nps_score_cohort(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0,
                      const nps_row_desc *rows, uint64_t n_desc, int mode);
 
 /* A score definition (the rows of one .scores file, nimpress.nim:247-254, plus what the host
- * found for each) kept on the device, so that re-scoring needs no host->device traffic. */
+ * found for each) kept on the device, so that re-scoring needs no host->device traffic.
+ * IEEE special values are scored as the reference scores them, in plain float64 (nimpress.nim:639-641): a beta of
+ * +-inf gives NaN where the dosage is 0 (0 x inf) and +-inf elsewhere, NaN propagates, a NaN imputed dosage times a zero
+ * beta stays NaN, nloci = 0 gives NaN, and sums that overflow are +-inf -- on every format and mode, NaN, +inf and -inf
+ * at the same samples as the reference's.  Rows the NPS_FMT_GT2X fixed-point kernels cannot carry (a non-finite beta,
+ * an infinite eaf, |beta| (4 + max(2, 2 |eaf|)) outside [2^-900, 2^1000)) are scored there in an IEEE double pass of
+ * their own after the fixed-point pass. */
 int nps_scoredef_create(nps_scoredef **out, int device, const nps_row_desc *rows, uint64_t n_desc);
 uint64_t nps_scoredef_n_present(const nps_scoredef *d); /* rows that consume a cohort row */
 void nps_scoredef_destroy(nps_scoredef *d);
@@ -355,7 +361,8 @@ int nps_score_cohort_def(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0
  * getImputedDosages, nimpress.nim:526-558: a constant, no genotypes) or NPS_ROW_NOT_IN_SCORE (the score
  * file does not list the locus).  Results per score are those of the single-score entry points
  * (same decisions, nloci bit-exact, scores within ~1e-13 relative: the weights are quantised to 2^-49 of
- * the largest one).  beta must be finite (NPS_E_UNSUPPORTED otherwise). */
+ * the largest one).  beta must be finite and eaf not infinite (NPS_E_UNSUPPORTED otherwise, naming the row; a NaN
+ * eaf is scored). */
 #define NPS_ROW_NOT_IN_SCORE 4
 #define NPS_MULTI_MAX_SCORES 8
 typedef struct nps_multi nps_multi;

@@ -176,6 +176,13 @@ struct nps_ctx {
     uint64_t mx_ops_cap = 0;                    // (in units of 48 bytes)
     double *d_mx_cblk = nullptr;                // ... and one partial sum of locus constants per superblock
     uint64_t mx_cblk_cap = 0;
+    // NPS_FMT_GT2X runs of a definition with special rows (nps_scoredef::special): those rows in the row layout, scored
+    // in IEEE double by the two-pass kernels, a batch at a time
+    uint32_t *d_sp_plain = nullptr;             // [batch][n_words] plain rows out of the strip layout
+    uint32_t *d_sp_group = nullptr;             // [batch / 4 groups][stride_words][4] interleaved
+    unsigned long long *d_sp_tally = nullptr;   // [batch]
+    double *d_sp_lut = nullptr;                 // [batch][4]
+    uint64_t sp_plain_cap = 0, sp_group_cap = 0, sp_tally_cap = 0, sp_lut_cap = 0;  // (elements)
     bool mx_plan_valid = false, mx_plan_two_pass = false;
     uint64_t mx_plan_m = 0;
     MxPlan mx_plan_cache{};
@@ -345,6 +352,10 @@ static void free_ctx(nps_ctx *c) {
     (void)hipFree(c->d_mx_tally1);
     (void)hipFree(c->d_mx_ops);
     (void)hipFree(c->d_mx_cblk);
+    (void)hipFree(c->d_sp_plain);
+    (void)hipFree(c->d_sp_group);
+    (void)hipFree(c->d_sp_tally);
+    (void)hipFree(c->d_sp_lut);
     (void)hipFree(c->d_rtally);
     (void)hipFree(c->d_rlut);
     (void)hipFree(c->d_rstats);
@@ -1448,8 +1459,26 @@ struct nps_scoredef {
         nps_row_desc *d_desc = nullptr;
     };
     std::vector<MxBand> mx_bands;
+    // ... and the PRESENT rows those kernels cannot carry (mx_special): their indices among the PRESENT rows, ascending,
+    // and their descriptors as given.  d_mx_desc is d_desc with these rows at beta = eaf = 0 (null: no special row);
+    // after the fixed-point pass mx_special_pass adds their products in IEEE double.
+    std::vector<uint64_t> special;
+    nps_row_desc *d_special = nullptr;
+    nps_row_desc *d_mx_desc = nullptr;
 };
 constexpr int kMxBandBits = 30, kMxMaxBands = 8;
+
+// A PRESENT row the fixed-point kernels of NPS_FMT_GT2X cohorts cannot carry: a non-finite beta (0 x inf is NaN, every
+// other dosage +-inf), an infinite eaf (the products of an imputed dosage are +-inf, and the kernels keep one NaN flag per
+// row), or a weight bound |beta| (4 + max(2, 2 |eaf|)) outside [2^-900, 2^1000): beyond the fixed-point scale 2^F,
+// |F| <= 1000, and beyond the overflow of the bound itself.  A NaN eaf is not special: its products are NaN.
+static bool mx_special(const nps_row_desc &r, double *bound) {
+    *bound = 0.0;
+    if (!std::isfinite(r.beta) || std::isinf(r.eaf)) return true;
+    const double ie = std::isfinite(r.eaf) ? std::max(2.0, 2.0 * std::fabs(r.eaf)) : 2.0;
+    *bound = std::fabs(r.beta) * (4.0 + ie);
+    return r.beta != 0.0 && !(*bound >= 0x1p-900 && *bound < 0x1p1000);
+}
 
 extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row_desc *rows,
                                    uint64_t n_desc) {
@@ -1469,11 +1498,12 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
         const nps_row_desc &r = rows[j];
         if (r.kind == NPS_ROW_PRESENT) {
             d->data_index[j] = (int64_t)data.size();
+            double bound = 0.0;
+            if (mx_special(r, &bound))
+                d->special.push_back(data.size());
+            else
+                d->mx_bound = std::max(d->mx_bound, bound);
             data.push_back(r);
-            if (std::isfinite(r.beta)) {
-                const double ie = std::isfinite(r.eaf) ? std::max(2.0, 2.0 * std::fabs(r.eaf)) : 2.0;
-                d->mx_bound = std::max(d->mx_bound, std::fabs(r.beta) * (4.0 + ie));
-            }
         } else if (r.kind == NPS_ROW_UNCOVERED || r.kind == NPS_ROW_ABSENT ||
                    r.kind == NPS_ROW_FILTERED) {
             d->data_index[j] = -1;
@@ -1492,6 +1522,20 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
         hipError_t e = hipMalloc(&d->d_desc, sizeof(nps_row_desc) * d->m);
         if (e == hipSuccess)
             e = hipMemcpy(d->d_desc, data.data(), sizeof(nps_row_desc) * d->m, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !d->special.empty()) {
+            const uint64_t k = d->special.size();
+            std::vector<nps_row_desc> sp(k);
+            for (uint64_t i = 0; i < k; ++i) {
+                sp[i] = data[d->special[i]];
+                data[d->special[i]].beta = 0.0;  // (from here on `data` is the fixed-point copy)
+                data[d->special[i]].eaf = 0.0;
+            }
+            e = hipMalloc(&d->d_special, sizeof(nps_row_desc) * k);
+            if (e == hipSuccess) e = hipMemcpy(d->d_special, sp.data(), sizeof(nps_row_desc) * k, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMalloc(&d->d_mx_desc, sizeof(nps_row_desc) * d->m);
+            if (e == hipSuccess)
+                e = hipMemcpy(d->d_mx_desc, data.data(), sizeof(nps_row_desc) * d->m, hipMemcpyHostToDevice);
+        }
         // magnitude bands for the fixed-point kernel (north star: 1e-6 RELATIVE for every sample, also one whose only
         // rows are the definition's smallest): band b holds the rows with bound 2^-30(b+1) < v <= bound 2^-30b
         std::vector<int> band(d->m, 0);
@@ -1531,6 +1575,8 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
         }
         if (e != hipSuccess) {
             (void)hipFree(d->d_desc);
+            (void)hipFree(d->d_special);
+            (void)hipFree(d->d_mx_desc);
             for (auto &mb : d->mx_bands) (void)hipFree(mb.d_desc);
             delete d;
             return fail(e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP,
@@ -1547,6 +1593,8 @@ extern "C" void nps_scoredef_destroy(nps_scoredef *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipFree(d->d_desc);
+    (void)hipFree(d->d_special);
+    (void)hipFree(d->d_mx_desc);
     for (auto &mb : d->mx_bands) (void)hipFree(mb.d_desc);
     delete d;
 }
@@ -1632,6 +1680,53 @@ static int ensure_resident_buffers(nps_ctx *c, uint64_t m_pad) {
     HIP_TRY(hipMalloc(&c->d_rlut, sizeof(double) * 4 * m_pad));
     HIP_TRY(hipMalloc(&c->d_rstats, sizeof(nps_locus_stat) * m_pad));
     c->res_cap = m_pad;
+    return NPS_OK;
+}
+
+// NPS_FMT_GT2X runs of a definition with special rows (mx_special): the fixed-point pass scored them at beta = eaf = 0 --
+// their tallies, statistics and decisions included, a product 0 x 0 is 0, and where it is NaN (an imputed NaN dosage) the
+// reference's product is NaN for any beta too.  Here the same rows come out of the strip layout into the row layout, a
+// batch at a time, and the two-pass row kernels add dosage x beta in IEEE double into the partial sums, with the
+// decisions of their own tallies of the same codes (nloci is counted once: by the fixed-point pass).
+static uint64_t mx_special_batch(const nps_ctx *c, uint64_t k) {
+    const uint64_t row_bytes = (c->n_words + c->stride_words) * 4;
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(4, (64ull << 20) / row_bytes / 4 * 4), 65532ull * 4);
+    return std::min(cap, (k + 3) / 4 * 4);
+}
+
+static int mx_special_buffers(nps_ctx *c, const nps_scoredef *def) {
+    const uint64_t B = mx_special_batch(c, def->special.size());
+    int rc = grow(c, (void **)&c->d_sp_plain, &c->sp_plain_cap, B * c->n_words, 4);
+    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_group, &c->sp_group_cap, B * c->stride_words, 4);
+    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_tally, &c->sp_tally_cap, B, sizeof(unsigned long long));
+    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_lut, &c->sp_lut_cap, 4 * B, sizeof(double));
+    return rc;
+}
+
+static int mx_special_pass(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                           unsigned long long *scratch_nloci) {
+    const uint64_t K = def->special.size(), B = mx_special_batch(c, K);
+    int rc = ensure_all_chunks(c);
+    if (rc) return rc;
+    ProfScope ps(c, P_ACCUM);
+    for (uint64_t b0 = 0; b0 < K; b0 += B) {
+        const uint64_t k = std::min(B, K - b0), k_pad = (k + 3) / 4 * 4;
+        for (uint64_t j = b0; j < b0 + k;) {  // one launch per run of consecutive rows
+            uint64_t e = j + 1;
+            while (e < b0 + k && def->special[e] == def->special[e - 1] + 1) ++e;
+            HIP_TRY(launch_gt2x_to_rows(c->stream, co->d_data, c->n, co->n_rows, cohort_row0 + def->special[j], e - j,
+                                        c->d_sp_plain + (j - b0) * c->n_words, c->n_words));
+            j = e;
+        }
+        HIP_TRY(launch_interleave_rows(c->stream, c->d_sp_plain, c->n_words, k, c->n, nullptr, c->d_sp_group,
+                                       c->stride_words));
+        HIP_TRY(launch_tally_packed(c->stream, c->d_sp_group, c->stride_words, c->n, k, c->d_sp_tally));
+        HIP_TRY(launch_row_params(c->stream, c->d_sp_tally, def->d_special + b0, k, k_pad, c->n, dev_params(c->params),
+                                  c->d_sp_lut, nullptr, scratch_nloci));
+        AccumGeom g = c->geom;
+        g.groups_per_chunk = std::max<uint32_t>(1, (uint32_t)((k_pad / 4 + g.n_chunks - 1) / g.n_chunks));
+        HIP_TRY(launch_accumulate(c->stream, c->d_sp_group, c->stride_words, k, c->d_sp_lut, g, c->d_part));
+    }
     return NPS_OK;
 }
 
@@ -1812,6 +1907,10 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
                 }
             }
         }
+        if (!def->special.empty()) {
+            rc = mx_special_buffers(c, def);
+            if (rc) return rc;
+        }
         if (mxp.given) {
             rc = grow(c, (void **)&c->d_mx_ops, &c->mx_ops_cap, m_pad, 48);
             if (rc == NPS_OK) rc = grow(c, (void **)&c->d_mx_cblk, &c->mx_cblk_cap, m_pad / 128, sizeof(double));
@@ -1877,7 +1976,7 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
         };
         std::vector<Run> runs;
         if (def->mx_bands.empty())
-            runs.push_back(Run{def->d_desc, def->mx_bound});
+            runs.push_back(Run{def->d_mx_desc ? def->d_mx_desc : def->d_desc, def->mx_bound});
         else
             for (const auto &mb : def->mx_bands) runs.push_back(Run{mb.d_desc, mb.bound});
         unsigned long long *scratch_nloci = reinterpret_cast<unsigned long long *>(c->d_mx_const);  // (the 8 scratch doubles)
@@ -1931,6 +2030,10 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
             }
             c->chunks_used = std::max(c->chunks_used, 1u);
             c->rtally_clean = true;
+        }
+        if (!def->special.empty()) {
+            rc = mx_special_pass(c, co, cohort_row0, def, scratch_nloci);
+            if (rc) return rc;
         }
         if (harvest && !mxp.given) {
             // the kept tallies are published only once they ARE in device memory (another context may score this cohort
@@ -2201,6 +2304,9 @@ extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const np
             if (!std::isfinite(r.beta))
                 return fail(NPS_E_UNSUPPORTED, "score %d row %llu: beta is not finite (use the single-score path)",
                             s, (unsigned long long)j);
+            if (std::isinf(r.eaf))  // (its imputed products are +-inf: the kernels keep one NaN flag; a NaN eaf is scored)
+                return fail(NPS_E_UNSUPPORTED, "score %d row %llu: eaf is infinite (use the single-score path)", s,
+                            (unsigned long long)j);
             maxb = std::max(maxb, std::fabs(r.beta));
             if (r.beta != 0.0) minb = std::min(minb, std::fabs(r.beta));
             if (std::isfinite(r.eaf)) maxe = std::max(maxe, std::fabs(r.eaf));

@@ -6,6 +6,7 @@ Same bars as tests/test_gpu_parity.py: tallies / decisions / nloci bit-exact, sc
 import numpy as np
 import pytest
 
+import score_compare
 from nimpress_amd import capi
 from oracle import refcpu
 from test_gpu_parity import PARAM_GRID, assert_stats_equal, make_cohort, oracle_scores, rel_err
@@ -23,11 +24,10 @@ def check_scores(scores, ref_scores, beta, nloci):
     of beta values with four decimals cancel to exactly zero for a few samples in 10^4; the reference's result for
     those is its own rounding noise, ~1e-20, and no other summation reproduces that to six digits.)"""
     got, ref = np.asarray(scores), np.asarray(ref_scores)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), "NaN positions differ"
-    ok = ~np.isnan(ref)
+    ok = score_compare.assert_special_equal(got, ref)  # (NaN, +inf, -inf at the same samples; ok: finite reference)
     if not ok.any():
         return 0
-    sb = float(np.sum(np.abs(beta))) / max(2.0 * nloci, 1.0)
+    sb = score_compare.beta_scale(beta, nloci)  # (over the finite betas)
     d = np.abs(got[ok] - ref[ok])
     plain = REL_TOL * np.maximum(np.abs(ref[ok]), 1e-12 * sb)
     tol = np.maximum(plain, 2.0 ** -50 * sb)

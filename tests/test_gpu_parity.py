@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import score_compare
 from nimpress_amd import capi
 from oracle import refcpu
 
@@ -20,14 +21,9 @@ REL_TOL = 1e-6
 
 
 def rel_err(got, ref, beta, nloci):
-    """max |d| / max(|ref|, 1e-12 * sum|beta| / (2 nloci))  -- SURVEY.md section 8(d)."""
-    got, ref = np.asarray(got), np.asarray(ref)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), "NaN positions differ"
-    ok = ~np.isnan(ref)
-    if not ok.any():
-        return 0.0
-    floor = 1e-12 * float(np.sum(np.abs(beta))) / max(2.0 * nloci, 1.0)
-    return float(np.max(np.abs(got[ok] - ref[ok]) / np.maximum(np.abs(ref[ok]), max(floor, 1e-300))))
+    """max |d| / max(|ref|, 1e-12 * sum|beta| / (2 nloci))  -- SURVEY.md section 8(d).
+    NaN, +inf and -inf must sit at the same samples, and the floor counts the finite betas only (tests/score_compare.py)"""
+    return score_compare.rel_err(got, ref, beta, nloci)
 
 
 def assert_stats_equal(gpu_stats, ref_stats):

@@ -106,13 +106,15 @@ def test_register_bound_kernels_do_not_spill(tmp_path):
     """Two kernels sit at their register limit by design and lose a third of their speed with the first spilled register:
     the float32 single-read DS kernel (128 VGPRs: sixteen waves per compute unit; round 5: a harmless-looking change of its
     ring's element type spilled 80 bytes per lane, 38 -> 61 ms) and the strip kernel.  The compiler's own resource remarks
-    must say ScratchSize 0 for them."""
+    must say ScratchSize 0 for them, and no more than its present 12 bytes per lane for the given-tallies strip kernel."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     want = {"nps_ds_fused.hip": ["ds_fused_kernelILi1024ELb0", "ds_fused_kernelILi960ELb0", "ds_fused_kernelILi896ELb0",
                                  "ds_fused_kernelILi1024ELb1"],
-            "nps_mx.hip": ["fused_mx_kernelILi0ELb0"]}
+            "nps_mx.hip": ["fused_mx_kernelILi0ELb0"],
+            # the given-tallies kernel spills 2 VGPRs (12 bytes per lane) today: the bound keeps it from growing
+            "nps_mxg.hip": [("mx_given_kernel", 12)]}
     for src, kernels in want.items():
         r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-Wno-unused-parameter",
                             "--cuda-device-only", "-c", os.path.join(CSRC, src), "-o", str(tmp_path / (src + ".o")),
@@ -127,6 +129,7 @@ def test_register_bound_kernels_do_not_spill(tmp_path):
             if m and name:
                 seen[name] = int(m.group(1))
         for k in kernels:
+            k, bound = k if isinstance(k, tuple) else (k, 0)
             hits = [v for nm, v in seen.items() if k in nm]
             assert hits, (src, k, sorted(seen))
-            assert all(v == 0 for v in hits), (src, k, hits)
+            assert all(v <= bound for v in hits), (src, k, hits, bound)
