@@ -258,7 +258,14 @@ void nps_destroy(nps_ctx *ctx);
  * a run whose resident grid (P = ceil(N / 2048) strips x floor(CUs / P) row teams) covers at least nine tenths of the
  * compute units counts its tallies in the pass (tallyAlleles, nimpress.nim:563, inside the one read), every time.  Other
  * sizes keep the cohort's tallies with the cohort -- NPS_MODE_AUTO ATTACHES this cache to the `const nps_cohort` it is given
- * (dropped by any call that rewrites rows; nps_cohort_has_tallies tells) -- and score later runs with the tallies given:
+ * (nps_cohort_has_tallies tells) -- and score later runs with the tallies given.  Validity is kept per superblock of 128 rows:
+ * rows that are UPLOADED or CONVERTED (nps_cohort_upload, _upload_bed, _convert) arrive with their tallies, counted by the
+ * kernel that writes them, and only the superblocks a call rewrites change state; rows from the synthetic generator carry
+ * none.  A run all of whose superblocks carry tallies is scored with them given when they were asked for
+ * (nps_cohort_keep_tallies, or a pass that kept them) or when the cohort has more than 262 144 samples (one row team per
+ * strip: P > 128); smaller cohorts serve their write-time tallies (nps_cohort_row_tallies) and count in the pass.  So an
+ * uploaded cohort of these sizes is scored in ONE read with the tallies given from its first pass on; what follows describes
+ * cohorts whose rows came without tallies (the generator):
  *   128 < P < 0.9 CUs (262 145 .. 471 040 samples on an MI355X): the first whole-cohort run
  *     is the single read in which the tallies are counted anyway and keeps them as a by-product (round 6: ONE read, 0.51 of
  *     the roofline at 300 000 samples, 0.65 at 400 000; until then a tally pass + a given-tallies pass, two reads, 0.38);
@@ -286,15 +293,20 @@ int nps_cohort_create(nps_cohort **out, int device, uint64_t n_samples, uint64_t
 uint64_t nps_cohort_row_stride(const nps_cohort *c);
 uint64_t nps_cohort_n_rows(const nps_cohort *c);
 int nps_cohort_format(const nps_cohort *c); /* NPS_FMT_* (never NPS_FMT_GT_AUTO) */
-/* copy rows [row0,row0+nrows) from host memory laid out with host_stride bytes per row */
+/* copy rows [row0,row0+nrows) from host memory laid out with host_stride bytes per row.  NPS_FMT_GT2X: the kernel that
+ * writes the units counts the rows' whole-row tallies (tallyAlleles, nimpress.nim:32-47) in the same pass: the superblocks
+ * written carry their tallies when the call returns (nps_cohort_rows_tallied, nps_cohort_row_tallies: the allele-frequency
+ * warnings of nimpress.nim:573-579 need no scoring pass), superblocks not written keep their state. */
 int nps_cohort_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *host_rows,
                       size_t host_stride);
 int nps_cohort_download(const nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows,
                         size_t host_stride);
 /* Rows of a PLINK 1 .bed file (variant-major; see nps_push_bed) -> rows [row0,row0+nrows) of a
- * NPS_FMT_GT2 cohort; effect_is_a1[j] selects the counted allele of row j.  A .bed file is already
+ * NPS_FMT_GT2 or NPS_FMT_GT2X cohort; effect_is_a1[j] is the code map (NPS_MAP_*) of row j.  A .bed file is already
  * 2-bit and sample-minor: bytes go over PCIe unchanged (pass the mmap'ed file + 3 header bytes,
- * row_stride_bytes = ceil(n_samples/4)) and are recoded + interleaved on the device. */
+ * row_stride_bytes = ceil(n_samples/4)) and are recoded + interleaved on the device.  NPS_FMT_GT2X: row0 a multiple of
+ * 128, rows after the end inside the last superblock written become zero, and the rows' tallies are counted while they are
+ * written, as for nps_cohort_upload. */
 int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrows, const uint8_t *bed_rows,
                           size_t row_stride_bytes, const uint8_t *effect_is_a1);
 /* One row of a NPS_FMT_GT2 cohort straight from the buffer a record holds -- the typed FORMAT/GT vector of a VCF/BCF
@@ -415,17 +427,23 @@ int nps_multi_reset(nps_multi *m, const nps_params *params /* NULL = keep */);
 void nps_multi_destroy(nps_multi *m);
 /* device time (HIP events) of the calls since the last reset: weight digits, the product, the fold */
 int nps_multi_timing(nps_multi *m, double *ms_params, double *ms_product, double *ms_fold);
-/* NPS_FMT_GT2 cohort (plain order) -> NPS_FMT_GT2M (with its row tallies) or NPS_FMT_GT2X cohort of the same shape */
+/* NPS_FMT_GT2 cohort (plain order) -> NPS_FMT_GT2M or NPS_FMT_GT2X cohort of the same shape, either with the whole-row
+ * tallies of every row, counted from the tiles the conversion moves anyway */
 int nps_cohort_convert(nps_cohort *dst, const nps_cohort *src);
 /* the whole-row tallies a NPS_FMT_GT2M cohort carries (tallyAlleles, nimpress.nim:32-47), for warnings; also those of a
- * NPS_FMT_GT2X cohort after nps_cohort_keep_tallies */
+ * NPS_FMT_GT2X cohort wherever every superblock (128 rows) of the range carries them -- written by nps_cohort_upload,
+ * _upload_bed or _convert since it was last rewritten, counted by nps_cohort_keep_tallies, or kept from a scoring pass: no
+ * scoring call is needed first.  NPS_E_UNSUPPORTED otherwise (nps_cohort_rows_tallied asks without failing). */
 int nps_cohort_row_tallies(const nps_cohort *c, uint64_t row0, uint64_t nrows, uint64_t *nmissing_out,
                            uint64_t *neffect_out);
 /* Count tallyAlleles (nimpress.nim:32-47, called per row at :563) of EVERY row of a NPS_FMT_GT2X cohort once and keep the
  * result with the cohort (one read of the matrix).  nps_score_cohort[_def] under NPS_MODE_AUTO then scores the cohort with
  * the tallies given -- no recount, no hand-over between the strips -- which is what many score files over one cohort want
- * (BASELINE configs[3]): the decision chain of getImputedDosages (:565-583) sees exactly the same counts.  Any call that
- * rewrites rows (upload, synth, convert) drops the kept tallies; NPS_MODE_FUSED / NPS_MODE_TWOPASS never use them.
+ * (BASELINE configs[3]): the decision chain of getImputedDosages (:565-583) sees exactly the same counts.  Only superblocks
+ * without tallies are counted: on a cohort that was uploaded or converted as a whole the call reads nothing and only records
+ * that the tallies are asked for (NPS_MODE_AUTO then uses them at ANY size).  A call that rewrites rows withdraws that mark;
+ * the superblocks it writes carry the new rows' tallies (upload, upload_bed, convert) or none (synth).  NPS_MODE_FUSED /
+ * NPS_MODE_TWOPASS never use kept tallies.
  * (Measured, round 6: it pays on cohorts of more than 262 144 samples -- 0.71-0.79 of the roofline against 0.51-0.73 in the
  * pass; below that the in-pass kernel is as fast or faster, and NPS_MODE_AUTO on its own never keeps tallies there.) */
 int nps_cohort_keep_tallies(nps_cohort *c);
@@ -438,7 +456,10 @@ int nps_cohort_keep_tallies(nps_cohort *c);
  * where it would not pay: cohorts of at most 262 144 samples (several row teams per strip: the given-tallies kernel is no
  * faster there than the pass that counts them). */
 int nps_cohort_expect_passes(nps_cohort *c, uint32_t n_passes);
-int nps_cohort_has_tallies(const nps_cohort *c); /* 1: the cohort carries whole-row tallies */
+int nps_cohort_has_tallies(const nps_cohort *c); /* 1: the WHOLE cohort carries whole-row tallies */
+/* 1: every superblock of rows [row0, row0+nrows) carries its tallies (nps_cohort_row_tallies succeeds), else 0.  (Added
+ * without a change of NPS_ABI_VERSION, like every symbol since version 1: the version counts incompatible changes.) */
+int nps_cohort_rows_tallied(const nps_cohort *c, uint64_t row0, uint64_t nrows);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 int nps_profile_enable(nps_ctx *ctx, int on); /* record HIP events around every launch */

@@ -63,7 +63,7 @@ SYMBOLS = [
     "nps_multi_finish", "nps_multi_finish_device", "nps_multi_reset", "nps_multi_destroy", "nps_multi_timing",
     "nps_cohort_convert", "nps_cohort_row_tallies", "nps_cohort_keep_tallies", "nps_cohort_has_tallies", "nps_multi_set_missing_weight_bits",
     "nps_cohort_push_gt_raw", "nps_cohort_push_bed", "nps_multi_partial_device", "nps_multi_partial",
-    "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes",
+    "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes", "nps_cohort_rows_tallied",
 ]
 
 
@@ -204,6 +204,7 @@ def load(with_torch: bool = True):
     L.nps_cohort_keep_tallies.argtypes = [vp]
     L.nps_cohort_expect_passes.argtypes = [vp, C.c_uint32]
     L.nps_cohort_has_tallies.argtypes = [vp]
+    L.nps_cohort_rows_tallied.argtypes = [vp, u64, u64]
     _lib = L
     return L
 
@@ -248,7 +249,8 @@ class Cohort:
         _check(load().nps_cohort_upload(self._h, row0, rows.shape[0], rows.ctypes.data, stride))
 
     def upload_bed(self, row0: int, bed_rows: np.ndarray, effect_is_a1):
-        """rows of a PLINK .bed file ([k, ceil(n/4)] uint8, e.g. a view of the mmap'ed file)"""
+        """rows of a PLINK .bed file ([k, ceil(n/4)] uint8, e.g. a view of the mmap'ed file) into a FMT_GT2 or a
+        FMT_GT2X cohort (row0 a multiple of 128 there)"""
         assert bed_rows.ndim == 2 and bed_rows.dtype == np.uint8 and bed_rows.strides[1] == 1
         flags = np.ascontiguousarray(effect_is_a1, dtype=np.uint8)
         assert flags.size == bed_rows.shape[0]
@@ -282,7 +284,7 @@ class Cohort:
         _check(load().nps_cohort_convert(self._h, src._h))
 
     def row_tallies(self, row0: int = 0, nrows: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """(nmissing, neffect) per row of a FMT_GT2M cohort"""
+        """(nmissing, neffect) per row of a FMT_GT2M cohort, or of rows of a FMT_GT2X cohort that carry them (rows_tallied)"""
         nrows = self.n_rows - row0 if nrows is None else nrows
         nm, ne = np.zeros(max(nrows, 1), dtype=np.uint64), np.zeros(max(nrows, 1), dtype=np.uint64)
         _check(load().nps_cohort_row_tallies(self._h, row0, nrows, nm.ctypes.data, ne.ctypes.data))
@@ -300,6 +302,10 @@ class Cohort:
 
     def has_tallies(self) -> bool:
         return bool(load().nps_cohort_has_tallies(self._h))
+
+    def rows_tallied(self, row0: int, nrows: int) -> bool:
+        """every superblock of rows [row0, row0 + nrows) carries its whole-row tallies (nps_cohort_rows_tallied)"""
+        return bool(load().nps_cohort_rows_tallied(self._h, int(row0), int(nrows)))
 
     def optimize(self):
         """one-time layout change (nps_cohort_optimize): parity layout of the high-bit planes, fewer LDS bank

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <mutex>
@@ -63,12 +64,19 @@ struct nps_cohort {
     bool optimized = false;
     // NPS_FMT_GT2M: whole-row tallies (nmissing << 32 | neffect) produced by whatever packed the rows
     unsigned long long *d_row_tally = nullptr;
-    // NPS_FMT_GT2X after nps_cohort_keep_tallies: the whole-row tallies (nmissing << 28 | neffect, the tally word of the
-    // strip kernel without its arrival count), one per row of every superblock; valid until rows are rewritten
+    // NPS_FMT_GT2X: the whole-row tallies (nmissing << 28 | neffect, the tally word of the strip kernel without its arrival
+    // count), one per row of every superblock, allocated (zeroed) on first need.  Counted where the rows are written
+    // (upload, upload_bed, convert: the fill kernels), by nps_cohort_keep_tallies, or kept from a scoring pass.
     unsigned long long *d_mx_row_tally = nullptr;
-    // (atomic: contexts on several threads may score one cohort; whoever finds the flag clear takes tally_mutex, the writer
-    //  publishes with release order AFTER the counted tallies are in device memory, readers load with acquire)
-    std::atomic<bool> mx_row_tally_valid{false};
+    // Which superblocks' words are complete: one bit per superblock (mx_sb_valid) and the number of bits set.  Contexts on
+    // several threads may score one cohort: every WRITER of d_mx_row_tally, of the bitmap and of mx_tally_asked holds
+    // tally_mutex and sets a bit (release) only AFTER the superblock's words are in device memory; readers load with
+    // acquire and never see a superblock valid whose words are still on their way.
+    std::unique_ptr<std::atomic<uint64_t>[]> mx_sb_valid;
+    std::atomic<uint64_t> mx_sb_valid_count{0};
+    // "asked for": nps_cohort_keep_tallies, or a pass that kept them (nps_cohort_expect_passes / the nine-tenths rule) --
+    // NPS_MODE_AUTO then scores valid runs with the tallies given at ANY size; cleared by every rewrite
+    std::atomic<bool> mx_tally_asked{false};
     std::mutex tally_mutex;  // NPS_MODE_AUTO may count them lazily from whichever context scores the cohort first
     std::atomic<uint32_t> expect_passes{0};  // nps_cohort_expect_passes: how often the caller will score this cohort (0: not said)
     // nps_cohort_push_*: rows decoded on the device straight into the cohort (a pinned ring the decode kernel reads
@@ -84,6 +92,49 @@ struct nps_cohort {
     std::vector<unsigned char> ds_row_bad;
     uint64_t ds_bad_rows = 0;
 };
+
+// ---- NPS_FMT_GT2X: which superblocks carry their tally words ------------------------------------------------------
+static bool mx_tallies_valid(const nps_cohort *c, uint64_t sb0, uint64_t n_sb) {
+    if (!c->mx_sb_valid) return n_sb == 0;
+    if (n_sb == gt2x_superblocks(c->n_rows)) return c->mx_sb_valid_count.load(std::memory_order_acquire) == n_sb;
+    for (uint64_t sb = sb0; sb < sb0 + n_sb; ++sb)
+        if (!((c->mx_sb_valid[sb >> 6].load(std::memory_order_acquire) >> (sb & 63)) & 1ull)) return false;
+    return true;
+}
+static bool mx_tallies_all_valid(const nps_cohort *c) { return mx_tallies_valid(c, 0, gt2x_superblocks(c->n_rows)); }
+// tally_mutex held.  valid = true only once the words of these superblocks ARE in device memory.
+static void mx_tallies_mark(nps_cohort *c, uint64_t sb0, uint64_t n_sb, bool valid) {
+    if (!c->mx_sb_valid) return;
+    uint64_t count = c->mx_sb_valid_count.load(std::memory_order_relaxed);
+    for (uint64_t sb = sb0; sb < sb0 + n_sb; ++sb) {
+        const uint64_t bit = 1ull << (sb & 63), w = c->mx_sb_valid[sb >> 6].load(std::memory_order_relaxed);
+        if (((w & bit) != 0) == valid) continue;
+        c->mx_sb_valid[sb >> 6].store(valid ? w | bit : w & ~bit, std::memory_order_release);
+        count += valid ? 1 : (uint64_t)-1;
+    }
+    c->mx_sb_valid_count.store(count, std::memory_order_release);
+}
+// tally_mutex held, the cohort's device current
+static hipError_t mx_tallies_alloc(nps_cohort *c) {
+    if (c->d_mx_row_tally) return hipSuccess;
+    const size_t bytes = sizeof(unsigned long long) * std::max<uint64_t>(gt2x_superblocks(c->n_rows) * 128, 1);
+    hipError_t e = hipMalloc(&c->d_mx_row_tally, bytes);
+    if (e == hipSuccess) e = hipMemset(c->d_mx_row_tally, 0, bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(c->d_mx_row_tally);
+        c->d_mx_row_tally = nullptr;
+    }
+    return e;
+}
+// a call that rewrites rows [row0, row0 + nrows) of a strip cohort: their superblocks carry nothing until the writer says so
+static void mx_tallies_rewrite(nps_cohort *c, uint64_t row0, uint64_t nrows) {
+    if (c->format != NPS_FMT_GT2X || nrows == 0) return;
+    std::lock_guard<std::mutex> lk(c->tally_mutex);
+    c->mx_tally_asked.store(false, std::memory_order_relaxed);
+    mx_tallies_mark(c, row0 >> 7, ((row0 + nrows + 127) >> 7) - (row0 >> 7), false);
+}
+
+static int mx_keep_tallies_locked(nps_cohort *c);
 
 static int cohort_quiesce(const nps_cohort *c) {
     if (c && c->push_stream) HIP_TRY(hipStreamSynchronize(c->push_stream));
@@ -1016,6 +1067,13 @@ extern "C" int nps_cohort_create(nps_cohort **out, int device, uint64_t n_sample
     if (format == NPS_FMT_GT2X) {
         c->stride_bytes = 0;  // not row-major: strips x superblocks x 1 KiB units
         bytes = std::max<uint64_t>(gt2x_bytes(n_samples, n_rows), 256);
+        const uint64_t words = (gt2x_superblocks(n_rows) + 63) / 64;
+        c->mx_sb_valid.reset(new (std::nothrow) std::atomic<uint64_t>[std::max<uint64_t>(words, 1)]);
+        if (!c->mx_sb_valid) {
+            delete c;
+            return fail(NPS_E_NOMEM, "out of host memory");
+        }
+        for (uint64_t w = 0; w < std::max<uint64_t>(words, 1); ++w) c->mx_sb_valid[w].store(0, std::memory_order_relaxed);
     }
     hipError_t e = hipMalloc(&c->d_data, bytes);
     if (e != hipSuccess) {
@@ -1155,33 +1213,59 @@ static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *
     return NPS_OK;
 }
 
-// NPS_FMT_GT2X: plain rows (C-ABI order and codes) <-> units, through a device staging buffer of whole superblocks
-static int gt2x_transfer(const nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows, size_t host_stride,
-                         bool to_device) {
-    if (to_device && (row0 & 127))
-        return fail(NPS_E_INVAL, "row0 must be a multiple of 128 for NPS_FMT_GT2X cohorts");
-    const uint64_t n_words = words_for(c->n_samples), sw = (n_words + 1) / 2 * 2;
+// NPS_FMT_GT2X: units -> plain rows (C-ABI order and codes), through a device staging buffer of whole superblocks
+static int gt2x_download(const nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows, size_t host_stride) {
+    const uint64_t n_words = words_for(c->n_samples), sw = (n_words + 3) / 4 * 4;
     const uint64_t chunk = std::max<uint64_t>(128, (256ull << 20) / (sw * 4) / 128 * 128);
     uint32_t *d_stage = nullptr;
     HIP_TRY(hipMalloc(&d_stage, std::min(chunk, (nrows + 127) / 128 * 128) * sw * 4));
     hipError_t e = hipSuccess;
     for (uint64_t r = 0; e == hipSuccess && r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        if (to_device) {
-            e = hipMemcpy2D(d_stage, sw * 4, (const char *)host_rows + r * host_stride, host_stride, n_words * 4, k,
-                            hipMemcpyHostToDevice);
-            if (e == hipSuccess)
-                e = launch_rows_to_gt2x(nullptr, d_stage, sw, c->n_samples, c->n_rows, row0 + r, k, c->d_data);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        } else {
-            e = launch_gt2x_to_rows(nullptr, c->d_data, c->n_samples, c->n_rows, row0 + r, k, d_stage, sw);
-            if (e == hipSuccess)
-                e = hipMemcpy2D((char *)host_rows + r * host_stride, host_stride, d_stage, sw * 4, n_words * 4, k,
-                                hipMemcpyDeviceToHost);
-        }
+        e = launch_gt2x_to_rows(nullptr, c->d_data, c->n_samples, c->n_rows, row0 + r, k, d_stage, sw);
+        if (e == hipSuccess)
+            e = hipMemcpy2D((char *)host_rows + r * host_stride, host_stride, d_stage, sw * 4, n_words * 4, k,
+                            hipMemcpyDeviceToHost);
     }
     (void)hipFree(d_stage);
     if (e != hipSuccess) return fail(NPS_E_HIP, "cohort transfer failed: %s", hipGetErrorString(e));
+    return NPS_OK;
+}
+
+// NPS_FMT_GT2X: host rows -> staging on the device -> units AND the rows' tally words (fill_gt2x_kernel), whole
+// superblocks at a time.  width = bytes of one source row; code_map: nullptr (rows of NPS_CODE_* codes) or a NPS_MAP_* per
+// row (.bed / .pgen rows).  The superblocks written are invalid from the start of the call and valid again -- with the new
+// rows' tallies -- once every launch has completed; superblocks the call does not touch keep their state.
+static int gt2x_fill(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *host_rows, size_t host_stride, size_t width,
+                     const uint8_t *code_map) {
+    if (row0 & 127) return fail(NPS_E_INVAL, "row0 must be a multiple of 128 for NPS_FMT_GT2X cohorts");
+    if (c->n_samples >= (1ull << 27)) return fail(NPS_E_UNSUPPORTED, "more than 2^27 samples");
+    const uint64_t n_words = words_for(c->n_samples), sw = (n_words + 3) / 4 * 4;
+    uint64_t chunk = std::max<uint64_t>(128, (256ull << 20) / (sw * 4) / 128 * 128);
+    chunk = std::min<uint64_t>(chunk, 128ull * 32768);
+    mx_tallies_rewrite(c, row0, nrows);
+    std::lock_guard<std::mutex> lk(c->tally_mutex);
+    HIP_TRY(mx_tallies_alloc(c));
+    const uint64_t sb0 = row0 >> 7, n_sb = (nrows + 127) / 128;
+    uint32_t *d_stage = nullptr;
+    uint8_t *d_map = nullptr;
+    HIP_TRY(hipMalloc(&d_stage, std::min(chunk, n_sb * 128) * sw * 4));
+    hipError_t e = hipSuccess;
+    if (code_map) e = hipMalloc(&d_map, std::min(chunk, nrows));
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_mx_row_tally + sb0 * 128, 0, sizeof(unsigned long long) * n_sb * 128, nullptr);
+    for (uint64_t r = 0; e == hipSuccess && r < nrows; r += chunk) {
+        const uint64_t k = std::min(chunk, nrows - r);
+        e = hipMemcpy2D(d_stage, sw * 4, (const char *)host_rows + r * host_stride, host_stride, width, k, hipMemcpyHostToDevice);
+        if (e == hipSuccess && code_map) e = hipMemcpy(d_map, code_map + r, k, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = launch_fill_gt2x_rows(nullptr, d_stage, sw, d_map, c->n_samples, c->n_rows, row0 + r, k, c->d_data,
+                                      c->d_mx_row_tally);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    (void)hipFree(d_stage);
+    (void)hipFree(d_map);
+    if (e != hipSuccess) return fail(NPS_E_HIP, "cohort transfer failed: %s", hipGetErrorString(e));
+    mx_tallies_mark(c, sb0, n_sb, true);
     return NPS_OK;
 }
 
@@ -1189,7 +1273,10 @@ extern "C" int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrow
                                      size_t row_stride_bytes, const uint8_t *effect_is_a1) {
     int rc = check_range(c, row0, nrows);
     if (rc) return rc;
-    if (c->format != NPS_FMT_GT2) return fail(NPS_E_INVAL, ".bed rows need a 2-bit (NPS_FMT_GT2) cohort");
+    if (c->format != NPS_FMT_GT2 && c->format != NPS_FMT_GT2X)
+        return fail(NPS_E_INVAL, ".bed rows need a 2-bit (NPS_FMT_GT2 or NPS_FMT_GT2X) cohort");
+    if (c->format == NPS_FMT_GT2X && (row0 & 127))
+        return fail(NPS_E_INVAL, "row0 must be a multiple of 128 for NPS_FMT_GT2X cohorts");
     const size_t width = (size_t)((c->n_samples + 3) / 4);
     if (nrows == 0 || width == 0) return NPS_OK;
     if (!bed_rows || !effect_is_a1 || row_stride_bytes < width)
@@ -1198,7 +1285,7 @@ extern "C" int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrow
         if (effect_is_a1[r] > NPS_MAP_PGEN_REF) return fail(NPS_E_INVAL, "row %llu: bad code map %d", (unsigned long long)r, (int)effect_is_a1[r]);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // no scoring kernel may still be reading the rows replaced here
-    c->mx_row_tally_valid = false;
+    if (c->format == NPS_FMT_GT2X) return gt2x_fill(c, row0, nrows, bed_rows, row_stride_bytes, width, effect_is_a1);
     rc = cohort_unoptimize(c);
     if (rc) return rc;
     return gt2_upload(c, row0, nrows, bed_rows, row_stride_bytes, width, effect_is_a1);
@@ -1338,14 +1425,13 @@ extern "C" int nps_cohort_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, c
     if (!host_rows || host_stride < width) return fail(NPS_E_INVAL, "bad host buffer / stride");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // no scoring kernel may still be reading the rows replaced here
-    c->mx_row_tally_valid = false;    // (kept tallies describe the rows as they were: nps_cohort_keep_tallies again)
     if (c->format == NPS_FMT_DS16) return ds16_transfer(c, row0, nrows, const_cast<void *>(host_rows), host_stride, true);
     if (c->format == NPS_FMT_GT2) {
         rc = cohort_unoptimize(c);
         if (rc) return rc;
         return gt2_upload(c, row0, nrows, host_rows, host_stride, width, nullptr);
     }
-    if (c->format == NPS_FMT_GT2X) return gt2x_transfer(c, row0, nrows, const_cast<void *>(host_rows), host_stride, true);
+    if (c->format == NPS_FMT_GT2X) return gt2x_fill(c, row0, nrows, host_rows, host_stride, width, nullptr);
     HIP_TRY(hipMemcpy2D((char *)c->d_data + row0 * c->stride_bytes, c->stride_bytes, host_rows,
                         host_stride, width, nrows, hipMemcpyHostToDevice));
     // the range of a dosage, row by row, where the rows now lie (one read at upload time, none when scoring)
@@ -1377,7 +1463,7 @@ extern "C" int nps_cohort_download(const nps_cohort *c, uint64_t row0, uint64_t 
     { int qrc = cohort_quiesce(c); if (qrc) return qrc; }
     if (c->format == NPS_FMT_DS16) return ds16_transfer(const_cast<nps_cohort *>(c), row0, nrows, host_rows, host_stride, false);
     if (c->format == NPS_FMT_GT2) return gt2_transfer(c, row0, nrows, host_rows, host_stride, false);
-    if (c->format == NPS_FMT_GT2X) return gt2x_transfer(c, row0, nrows, host_rows, host_stride, false);
+    if (c->format == NPS_FMT_GT2X) return gt2x_download(c, row0, nrows, host_rows, host_stride);
     HIP_TRY(hipMemcpy2D(host_rows, host_stride, (const char *)c->d_data + row0 * c->stride_bytes,
                         c->stride_bytes, width, nrows, hipMemcpyDeviceToHost));
     return NPS_OK;
@@ -1396,7 +1482,9 @@ extern "C" int nps_cohort_synth_rows(nps_cohort *c, uint64_t row0, uint64_t nrow
         return fail(NPS_E_INVAL, "row0 must be a multiple of 128 for NPS_FMT_GT2M / NPS_FMT_GT2X cohorts");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // no scoring kernel may still be reading the rows replaced here
-    c->mx_row_tally_valid = false;
+    // (a strip cohort's generator counts nothing, on purpose: the superblocks it writes carry no tallies afterwards and a
+    //  synthetic cohort is scored as it always was -- counted in the pass, or once by the first pass that wants them kept)
+    mx_tallies_rewrite(c, row0, nrows);
     rc = cohort_unoptimize(c);
     if (rc) return rc;
     uint32_t *d_t = nullptr;
@@ -1767,10 +1855,21 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
     MxPlan mxp;
     bool kept_tallies = false, harvest = false;
     if (is_mx && m && c->n) {
-        // a cohort that carries its tallies (nps_cohort_keep_tallies) is scored with them given under NPS_MODE_AUTO: the
-        // "two-pass" plan (independent workgroups) without its tally pass
-        kept_tallies = co->mx_row_tally_valid.load(std::memory_order_acquire) && mode == NPS_MODE_AUTO;
-        if (!kept_tallies && mode == NPS_MODE_AUTO) {
+        // A run whose superblocks all carry their tallies is scored with them given under NPS_MODE_AUTO -- the "two-pass" plan
+        // (independent workgroups) without its tally pass -- when the tallies were asked for (nps_cohort_keep_tallies, a pass
+        // that kept them: any size), or when they came with the rows (upload, upload_bed, convert) and a strip has ONE row
+        // team: only there is the given-tallies kernel faster than the pass that counts them (`one_team` below).  Smaller
+        // cohorts keep and serve their write-time tallies (nps_cohort_row_tallies) and are scored in the pass.
+        const bool run_valid = mode == NPS_MODE_AUTO && mx_tallies_valid(co, cohort_row0 >> 7, (m + 127) / 128);
+        if (run_valid) {
+            kept_tallies = co->mx_tally_asked.load(std::memory_order_acquire);
+            if (!kept_tallies) {
+                MxPlan p1;
+                HIP_TRY(mx_plan(c->device, c->n, m, false, &p1));
+                kept_tallies = p1.ok && (p1.given || p1.Q == 1);
+            }
+        }
+        if (!run_valid && mode == NPS_MODE_AUTO) {
             // Does the single-read kernel's resident grid cover the chip at this size, and will the cohort be scored again?
             //   * a resident grid exists (P <= compute units) and the run covers the whole cohort: the pass counts the tallies
             //     anyway -- where later passes want them given (the grid covers less than nine tenths of the chip, or the
@@ -1800,11 +1899,9 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
                 } else if ((p1.given || (!covers && m >= 16384)) && m * 4 >= co->n_rows) {
                     nps_cohort *mco = const_cast<nps_cohort *>(co);
                     std::lock_guard<std::mutex> lk(mco->tally_mutex);
-                    if (!mco->mx_row_tally_valid.load(std::memory_order_acquire)) {
-                        rc = nps_cohort_keep_tallies(mco);
-                        if (rc) return rc;
-                        HIP_TRY(hipSetDevice(c->device));
-                    }
+                    rc = mx_keep_tallies_locked(mco);  // (counts what is not valid yet: nothing, if another thread was first)
+                    if (rc) return rc;
+                    HIP_TRY(hipSetDevice(c->device));
                     kept_tallies = true;
                 }
             }
@@ -1899,12 +1996,9 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
         if (harvest) {  // (the cohort's kept tallies: allocated once, by whoever harvests first)
             nps_cohort *mco = const_cast<nps_cohort *>(co);
             std::lock_guard<std::mutex> lk(mco->tally_mutex);
-            if (!mco->d_mx_row_tally) {
-                if (hipMalloc(&mco->d_mx_row_tally, sizeof(unsigned long long) * gt2x_superblocks(co->n_rows) * 128) != hipSuccess) {
-                    (void)hipGetLastError();
-                    mco->d_mx_row_tally = nullptr;
-                    harvest = false;  // (no room: the pass runs as it always did)
-                }
+            if (mx_tallies_alloc(mco) != hipSuccess) {
+                (void)hipGetLastError();
+                harvest = false;  // (no room: the pass runs as it always did)
             }
         }
         if (!def->special.empty()) {
@@ -2038,8 +2132,13 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
         if (harvest && !mxp.given) {
             // the kept tallies are published only once they ARE in device memory (another context may score this cohort
             // from another thread and stream): one wait, on the cohort's first pass only
+            // (a superblock that was valid before -- rows uploaded, then others rewritten by the generator -- has received the
+            //  same words again: a reader on another thread sees complete words at every moment)
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const_cast<nps_cohort *>(co)->mx_row_tally_valid.store(true, std::memory_order_release);
+            nps_cohort *mco = const_cast<nps_cohort *>(co);
+            std::lock_guard<std::mutex> lk(mco->tally_mutex);
+            mx_tallies_mark(mco, 0, gt2x_superblocks(co->n_rows), true);
+            mco->mx_tally_asked.store(true, std::memory_order_release);
         }
         return done();
     }
@@ -2202,11 +2301,17 @@ extern "C" int nps_cohort_convert(nps_cohort *dst, const nps_cohort *src) {
     { int qrc = cohort_quiesce(src); if (qrc) return qrc; }
     HIP_TRY(hipDeviceSynchronize());
     if (src->n_rows == 0 || src->n_samples == 0) return NPS_OK;
-    dst->mx_row_tally_valid = false;
-    if (dst->format == NPS_FMT_GT2X) {
-        HIP_TRY(launch_gt2_to_gt2x(nullptr, (const uint32_t *)src->d_data, src->stride_bytes / 4, src->n_samples,
-                                   src->n_rows, dst->d_data));
+    if (dst->format == NPS_FMT_GT2X) {  // units and, from the same tiles, the tally words of every superblock
+        if (dst->n_samples >= (1ull << 27)) return fail(NPS_E_UNSUPPORTED, "more than 2^27 samples");
+        mx_tallies_rewrite(dst, 0, dst->n_rows);
+        std::lock_guard<std::mutex> lk(dst->tally_mutex);
+        const uint64_t n_sb = gt2x_superblocks(dst->n_rows);
+        HIP_TRY(mx_tallies_alloc(dst));
+        HIP_TRY(hipMemsetAsync(dst->d_mx_row_tally, 0, sizeof(unsigned long long) * n_sb * 128, nullptr));
+        HIP_TRY(launch_fill_gt2x_from_gt2(nullptr, (const uint32_t *)src->d_data, src->stride_bytes / 4, src->n_samples,
+                                          src->n_rows, dst->d_data, dst->d_mx_row_tally));
         HIP_TRY(hipDeviceSynchronize());
+        mx_tallies_mark(dst, 0, n_sb, true);
         return NPS_OK;
     }
     // units and, from the same tiles, the whole-row tallies (tallyAlleles nimpress.nim:32-47)
@@ -2220,10 +2325,11 @@ extern "C" int nps_cohort_row_tallies(const nps_cohort *c, uint64_t row0, uint64
                                       uint64_t *neffect_out) {
     int rc = check_range(c, row0, nrows);
     if (rc) return rc;
-    const bool kept = c->format == NPS_FMT_GT2X && c->mx_row_tally_valid;
+    const bool kept = c->format == NPS_FMT_GT2X && nps_cohort_rows_tallied(c, row0, nrows);
     if (c->format != NPS_FMT_GT2M && !kept)
-        return fail(NPS_E_UNSUPPORTED, "row tallies are kept with NPS_FMT_GT2M cohorts, and with NPS_FMT_GT2X cohorts after "
-                                       "nps_cohort_keep_tallies");
+        return fail(NPS_E_UNSUPPORTED, "row tallies are kept with NPS_FMT_GT2M cohorts, and with the superblocks of a "
+                                       "NPS_FMT_GT2X cohort that were uploaded / converted or counted since they were last "
+                                       "written (nps_cohort_rows_tallied tells; nps_cohort_keep_tallies counts the rest)");
     if (nrows == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<unsigned long long> t(nrows);
@@ -2240,29 +2346,48 @@ extern "C" int nps_cohort_row_tallies(const nps_cohort *c, uint64_t row0, uint64
 // nimpress.nim:32-47, of every row over all samples), counted ONCE by mx_tally_kernel.  nps_score_cohort[_def] with
 // NPS_MODE_AUTO then scores the cohort with the tallies given: one read of the matrix, no popcounts, no hand-over
 // between the strips, an ordinary grid.  For many score files over one cohort (BASELINE configs[3]: tally once, score
-// eight times).  Rewriting rows (upload, synth, convert) drops the tallies.
+// eight times).  Rows that are uploaded or converted bring their tallies along (the fill kernels count while they write: nothing is
+// read here for them); the generator's rows do not.
+// tally_mutex held: counts the superblocks that are not valid (nothing where all are: no read) and sets the mark
+static int mx_keep_tallies_locked(nps_cohort *c) {
+    const uint64_t n_sb = gt2x_superblocks(c->n_rows);
+    if (c->n_samples >= (1ull << 27)) return fail(NPS_E_UNSUPPORTED, "more than 2^27 samples");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!mx_tallies_all_valid(c)) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(mx_tallies_alloc(c));
+        if (c->n_samples) {
+            MxPlan mp;
+            HIP_TRY(mx_plan(c->device, c->n_samples, c->n_rows, true, &mp));
+            if (!mp.ok) return fail(NPS_E_UNSUPPORTED, "shape beyond the NPS_FMT_GT2X kernels");
+            // every maximal range of superblocks without tallies: valid words are never touched (a context on another
+            // thread may be scoring from them)
+            for (uint64_t sb = 0; sb < n_sb;) {
+                if (mx_tallies_valid(c, sb, 1)) {
+                    ++sb;
+                    continue;
+                }
+                uint64_t e = sb + 1;
+                while (e < n_sb && !mx_tallies_valid(c, e, 1)) ++e;
+                HIP_TRY(hipMemsetAsync(c->d_mx_row_tally + sb * 128, 0, sizeof(unsigned long long) * (e - sb) * 128, nullptr));
+                mp.n_sb = (uint32_t)(e - sb);
+                HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data, n_sb, sb, c->n_samples, c->d_mx_row_tally + sb * 128));
+                sb = e;
+            }
+            HIP_TRY(hipDeviceSynchronize());
+        }
+        mx_tallies_mark(c, 0, n_sb, true);
+    }
+    c->mx_tally_asked.store(true, std::memory_order_release);
+    return NPS_OK;
+}
 extern "C" int nps_cohort_keep_tallies(nps_cohort *c) {
     if (!c) return fail(NPS_E_INVAL, "cohort is NULL");
     if (c->format != NPS_FMT_GT2X)
         return fail(NPS_E_UNSUPPORTED, "nps_cohort_keep_tallies is for NPS_FMT_GT2X cohorts (NPS_FMT_GT2M carries its tallies "
                                        "from the packer; the other layouts count while they read)");
-    if (c->n_rows == 0 || c->n_samples == 0) {
-        c->mx_row_tally_valid = true;
-        return NPS_OK;
-    }
-    if (c->n_samples >= (1ull << 27)) return fail(NPS_E_UNSUPPORTED, "more than 2^27 samples");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const uint64_t n_sb = gt2x_superblocks(c->n_rows);
-    if (!c->d_mx_row_tally) HIP_TRY(hipMalloc(&c->d_mx_row_tally, sizeof(unsigned long long) * n_sb * 128));
-    HIP_TRY(hipMemset(c->d_mx_row_tally, 0, sizeof(unsigned long long) * n_sb * 128));
-    MxPlan mp;
-    HIP_TRY(mx_plan(c->device, c->n_samples, c->n_rows, true, &mp));
-    if (!mp.ok) return fail(NPS_E_UNSUPPORTED, "shape beyond the NPS_FMT_GT2X kernels");
-    HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data, n_sb, 0, c->n_samples, c->d_mx_row_tally));
-    HIP_TRY(hipDeviceSynchronize());
-    c->mx_row_tally_valid = true;
-    return NPS_OK;
+    std::lock_guard<std::mutex> lk(c->tally_mutex);
+    return mx_keep_tallies_locked(c);
 }
 extern "C" int nps_cohort_expect_passes(nps_cohort *c, uint32_t n_passes) {
     if (!c) return fail(NPS_E_INVAL, "cohort is NULL");
@@ -2270,7 +2395,17 @@ extern "C" int nps_cohort_expect_passes(nps_cohort *c, uint32_t n_passes) {
     return NPS_OK;
 }
 extern "C" int nps_cohort_has_tallies(const nps_cohort *c) {
-    return c && (c->format == NPS_FMT_GT2M || (c->format == NPS_FMT_GT2X && c->mx_row_tally_valid)) ? 1 : 0;
+    if (!c) return 0;
+    if (c->format == NPS_FMT_GT2M) return 1;
+    if (c->format != NPS_FMT_GT2X || !mx_tallies_all_valid(c)) return 0;
+    return c->n_rows || c->mx_tally_asked.load(std::memory_order_acquire) ? 1 : 0;  // (no rows: once asked for, as before)
+}
+extern "C" int nps_cohort_rows_tallied(const nps_cohort *c, uint64_t row0, uint64_t nrows) {
+    if (!c || row0 > c->n_rows || nrows > c->n_rows - row0) return 0;
+    if (c->format == NPS_FMT_GT2M) return 1;
+    if (c->format != NPS_FMT_GT2X) return 0;
+    if (nrows == 0) return nps_cohort_has_tallies(c);
+    return mx_tallies_valid(c, row0 >> 7, ((row0 + nrows + 127) >> 7) - (row0 >> 7)) ? 1 : 0;
 }
 
 struct nps_multidef {

@@ -340,11 +340,16 @@ hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const void *d_uni
 hipError_t launch_synth_gt2x(hipStream_t st, void *d_units, uint64_t n_samples, uint64_t n_rows_cohort, uint64_t row0,
                              uint64_t gen_row0, uint64_t n_rows, uint64_t seed, const uint32_t *d_t_het,
                              const uint32_t *d_t_hom, const uint32_t *d_t_miss);
-hipError_t launch_rows_to_gt2x(hipStream_t st, const uint32_t *d_src, uint64_t src_stride_words, uint64_t n_samples,
-                               uint64_t n_rows_cohort, uint64_t row0, uint64_t n_rows, void *d_units);
+// fill-and-tally (fill_gt2x_kernel): plain rows of NPS_CODE_* codes (d_map null) or PLINK .bed / .pgen rows (d_map: a
+// NPS_MAP_* per row), row-major on the device, src_stride_words (a multiple of 4) apart -> units AND the rows' tally words
+// (nmissing << 28 | neffect) added into d_tally[row0 ..]: the words of the superblocks written must be zero on entry
+hipError_t launch_fill_gt2x_rows(hipStream_t st, const uint32_t *d_src, uint64_t src_stride_words, const uint8_t *d_map,
+                                 uint64_t n_samples, uint64_t n_rows_cohort, uint64_t row0, uint64_t n_rows, void *d_units,
+                                 unsigned long long *d_tally);
 hipError_t launch_gt2x_to_rows(hipStream_t st, const void *d_units, uint64_t n_samples, uint64_t n_rows_cohort,
                                uint64_t row0, uint64_t n_rows, uint32_t *d_dst, uint64_t dst_stride_words);
-hipError_t launch_gt2_to_gt2x(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
-                              uint64_t n_rows, void *d_units);
+// a whole NPS_FMT_GT2 cohort (plain order) -> units and tally words (d_tally: [n_sb * 128], zero on entry)
+hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
+                                     uint64_t n_rows, void *d_units, unsigned long long *d_tally);
 
 }  // namespace nps

@@ -679,25 +679,98 @@ __global__ __launch_bounds__(256) void synth_gt2x_kernel(unsigned long long *__r
     units[gt2x_unit_index(unit, sb0 + sb, n_units, n_sb) * 128 + rho] = out;
 }
 
-// plain rows (C-ABI order and codes, row stride src_stride_words) -> units; rows past n_rows of the last
-// superblock become zero.  One thread = one row of one unit.
-__global__ __launch_bounds__(256) void rows_to_gt2x_kernel(const uint32_t *__restrict__ src, uint64_t src_stride_words,
-                                                           uint64_t n_words, uint64_t n_rows,
-                                                           unsigned long long *__restrict__ units, uint64_t n_units,
-                                                           uint64_t n_sb, uint64_t sb0) {
-    const uint64_t unit = (uint64_t)blockIdx.x * 2 + (threadIdx.x >> 7);
-    const uint32_t rho = threadIdx.x & 127;
-    const uint64_t sb = blockIdx.y;
-    if (unit >= n_units) return;
-    const uint64_t r = sb * 128 + rho;
-    unsigned long long out = 0;
-    if (r < n_rows) {
-        const uint32_t *p = src + r * src_stride_words + unit * 2;
-        const unsigned long long lo = unit * 2 < n_words ? p[0] : 0u, hi = unit * 2 + 1 < n_words ? p[1] : 0u;
-        const unsigned long long x = lo | (hi << 32);
-        out = x ^ ((x >> 1) & 0x5555555555555555ull);  // NPS_CODE_* (2 = missing, 3 = dosage 2) -> 2 = dosage 2, 3 = missing
+// ---- fill kernels: the units AND the rows' whole-row tallies from one pass over the source ------------------------
+// What fills a strip cohort with real rows -- plain C-ABI rows, PLINK .bed / .pgen rows with a per-row code map (NPS_MAP_*),
+// a NPS_FMT_GT2 cohort -- touches every genotype anyway: the tally word mx_given_kernel reads (nmissing << 28 | neffect,
+// tallyAlleles nimpress.nim:32-47) is counted here, so that the first scoring pass already runs with the tallies given.
+// Workgroup = one superblock x a group of 16 strips (what mx_tally_kernel takes): it walks the group in tiles of 128 rows
+// x 32 source words (16 units).  A tile comes in as 128-byte pieces of rows (row sources) or 512-byte pieces of row groups
+// (NPS_FMT_GT2), goes through LDS, and every unit leaves as 1 KiB of consecutive rows.  A thread keeps ONE row (tid & 127)
+// through all tiles: its counts stay in two registers, the two halves of the workgroup meet in LDS, and the workgroup
+// adds one word per row -- one global atomic per row per 16 strips.  Counted in strip codes AFTER the padding samples of
+// the last unit are cleared; rows past the end of the source (the padding rows of the last superblock) are zero and count
+// nothing.
+enum { kFillRows = 0, kFillBed = 1, kFillGt2 = 2 };
+constexpr uint32_t kFillStrips = 16;
+
+// a .bed / .pgen word pair (32 samples) -> NPS_CODE_* codes (bed_recode of nps_kernels.hip, 64 bits wide)
+static __device__ __forceinline__ unsigned long long bed_recode64(unsigned long long w, int map) {
+    const unsigned long long m = 0x5555555555555555ull, h = (w >> 1) & m, l = w & m;
+    switch (map) {
+    case 1: return ~w;
+    case 2: return w ^ h;
+    case 3: return ((~(h ^ l) & m) << 1) | (~h & m);
+    default: return h | (l << 1);
     }
-    units[gt2x_unit_index(unit, sb0 + sb, n_units, n_sb) * 128 + rho] = out;
+}
+
+// src: SRC = kFillRows / kFillBed: row-major staging rows, n_cols uint4 per row (src_stride4 apart), rows [0, n_src_rows) of
+// it are superblocks src_sb0.. of the source; kFillGt2: the NPS_FMT_GT2 cohort, one uint4 per (row group, word column),
+// n_cols = words per row, n_src_rows = its rows.  tally: the cohort's tally words (those of the superblocks written are zero).
+template <int SRC>
+__global__ __launch_bounds__(256) void fill_gt2x_kernel(const uint4 *__restrict__ src, uint64_t src_stride4, uint64_t n_cols,
+                                                        uint64_t n_src_rows, uint64_t src_sb0,
+                                                        const uint8_t *__restrict__ map, uint64_t n_samples,
+                                                        unsigned long long *__restrict__ units, uint64_t n_units,
+                                                        uint64_t n_sb, uint64_t dst_sb0,
+                                                        unsigned long long *__restrict__ tally) {
+    __shared__ uint32_t tile[128][33];  // [row][word column], padded
+    __shared__ uint32_t s_eff[128], s_mis[128];
+    const int t = threadIdx.x, rho = t & 127;
+    const uint64_t sb_src = src_sb0 + blockIdx.y, sb_dst = dst_sb0 + blockIdx.y;
+    const uint64_t unit_lo = (uint64_t)blockIdx.x * (kFillStrips * 64);
+    const uint64_t unit_hi = unit_lo + kFillStrips * 64 < n_units ? unit_lo + kFillStrips * 64 : n_units;
+    const uint64_t row = sb_src * 128 + rho;  // this thread's row in the source
+    const bool live = row < n_src_rows;
+    int code_map = 0;
+    if (SRC == kFillBed && live) code_map = map[row];
+    if (t < 128) s_eff[t] = s_mis[t] = 0u;
+    uint32_t n_l = 0, n_h = 0, n_m = 0;  // samples with the low code bit, the high one, both (= missing)
+    for (uint64_t u0 = unit_lo; u0 < unit_hi; u0 += 16) {
+        __syncthreads();  // (the tile's last readers; the first time: the zeroed sums)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = t + 256 * i;
+            if (SRC == kFillGt2) {  // (row group 0..31, word column 0..31)
+                const uint64_t rg = sb_src * 32 + (e >> 5), c = u0 * 2 + (e & 31);
+                uint4 q = make_uint4(0, 0, 0, 0);
+                if (rg * 4 < n_src_rows && c < n_cols) q = src[rg * src_stride4 + c];
+                const int r = 4 * (e >> 5);
+                tile[r][e & 31] = q.x, tile[r + 1][e & 31] = q.y, tile[r + 2][e & 31] = q.z, tile[r + 3][e & 31] = q.w;
+            } else {  // (row 0..127, four word columns)
+                const uint64_t r = sb_src * 128 + (e >> 3), c4 = u0 / 2 + (e & 7);
+                uint4 q = make_uint4(0, 0, 0, 0);
+                if (r < n_src_rows && c4 < n_cols) q = src[r * src_stride4 + c4];
+                uint32_t *p = &tile[e >> 3][4 * (e & 7)];
+                p[0] = q.x, p[1] = q.y, p[2] = q.z, p[3] = q.w;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int u = (t >> 7) + 2 * i;
+            const uint64_t unit = u0 + u;
+            if (unit >= unit_hi) continue;
+            unsigned long long lo = tile[rho][2 * u], hi = tile[rho][2 * u + 1];
+            if (SRC == kFillGt2) lo = word_from_planes((uint32_t)lo), hi = word_from_planes((uint32_t)hi);
+            unsigned long long x = lo | (hi << 32);
+            if (SRC == kFillBed) x = bed_recode64(x, code_map);
+            const uint64_t left = n_samples - unit * 32;  // (>= 1: unit < n_units)
+            if (left < 32) x &= (1ull << (2 * left)) - 1ull;
+            if (!live) x = 0ull;
+            x ^= (x >> 1) & 0x5555555555555555ull;  // NPS_CODE_* (2 = missing, 3 = dosage 2) -> 2 = dosage 2, 3 = missing
+            units[gt2x_unit_index(unit, sb_dst, n_units, n_sb) * 128 + rho] = x;
+            const unsigned long long l = x & 0x5555555555555555ull, h = (x >> 1) & 0x5555555555555555ull;
+            n_l += (uint32_t)__popcll(l);
+            n_h += (uint32_t)__popcll(h);
+            n_m += (uint32_t)__popcll(l & h);
+        }
+    }
+    atomicAdd(&s_eff[rho], n_l + 2u * n_h - 3u * n_m);
+    atomicAdd(&s_mis[rho], n_m);
+    __syncthreads();
+    if (t < 128 && (s_eff[t] | s_mis[t]))
+        atomicAdd(&tally[sb_dst * 128 + t], ((unsigned long long)s_mis[t] << 28) | (unsigned long long)s_eff[t]);
 }
 
 __global__ __launch_bounds__(256) void gt2x_to_rows_kernel(const unsigned long long *__restrict__ units, uint64_t n_units,
@@ -713,38 +786,6 @@ __global__ __launch_bounds__(256) void gt2x_to_rows_kernel(const unsigned long l
     uint32_t *p = dst + r * dst_stride_words + unit * 2;
     if (unit * 2 < n_words) p[0] = (uint32_t)x;
     if (unit * 2 + 1 < n_words) p[1] = (uint32_t)(x >> 32);
-}
-
-// a NPS_FMT_GT2 cohort (group-interleaved, plane-separated words, plain layout) -> units.  Workgroup = one superblock
-// x 32 word columns (16 units): the 128 x 32 word tile comes in as 32 row groups x 512 contiguous bytes (a thread that
-// fetches its own two words reads 32-byte pieces: 3.7 TB/s read + written), goes through LDS, and every unit leaves as
-// 1 KiB of consecutive rows.
-__global__ __launch_bounds__(256) void gt2_to_gt2x_kernel(const uint4 *__restrict__ src, uint64_t stride_words,
-                                                          uint64_t n_words, uint64_t n_row_groups,
-                                                          unsigned long long *__restrict__ units, uint64_t n_units,
-                                                          uint64_t n_sb, uint64_t sb_off) {
-    __shared__ uint32_t tile[128][33];  // [row][word column], padded
-    const int t = threadIdx.x;
-    const uint64_t sb = sb_off + blockIdx.y, c0 = (uint64_t)blockIdx.x * 32;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = t + 256 * i;  // (row group 0..31, column 0..31)
-        const uint64_t rg = sb * 32 + (e >> 5), c = c0 + (e & 31);
-        uint4 q = make_uint4(0, 0, 0, 0);
-        if (rg < n_row_groups && c < n_words) q = src[rg * stride_words + c];
-        const int r = 4 * (e >> 5);
-        tile[r][e & 31] = q.x, tile[r + 1][e & 31] = q.y, tile[r + 2][e & 31] = q.z, tile[r + 3][e & 31] = q.w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int e = t + 256 * i, u = e >> 7, rho = e & 127;
-        const uint64_t unit = (uint64_t)blockIdx.x * 16 + u;
-        if (unit >= n_units) continue;
-        const unsigned long long lo = word_from_planes(tile[rho][2 * u]), hi = word_from_planes(tile[rho][2 * u + 1]);
-        const unsigned long long x = lo | (hi << 32);
-        units[gt2x_unit_index(unit, sb, n_units, n_sb) * 128 + rho] = x ^ ((x >> 1) & 0x5555555555555555ull);
-    }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
@@ -769,17 +810,26 @@ hipError_t launch_synth_gt2x(hipStream_t st, void *d_units, uint64_t n_samples, 
     return hipGetLastError();
 }
 
-hipError_t launch_rows_to_gt2x(hipStream_t st, const uint32_t *d_src, uint64_t src_stride_words, uint64_t n_samples,
-                               uint64_t n_rows_cohort, uint64_t row0, uint64_t n_rows, void *d_units) {
+hipError_t launch_fill_gt2x_rows(hipStream_t st, const uint32_t *d_src, uint64_t src_stride_words, const uint8_t *d_map,
+                                 uint64_t n_samples, uint64_t n_rows_cohort, uint64_t row0, uint64_t n_rows, void *d_units,
+                                 unsigned long long *d_tally) {
     if (n_rows == 0 || n_samples == 0) return hipSuccess;
-    if (row0 & 127) return hipErrorInvalidValue;
     const MxGeom gm = mx_geom(n_samples, n_rows_cohort);
-    dim3 grid;
-    hipError_t e = grid_2d(gm.n_units, (n_rows + 127) / 128, &grid);
-    if (e != hipSuccess) return e;
+    const uint64_t k = (n_rows + 127) / 128;
+    if ((row0 & 127) || (src_stride_words & 3) || src_stride_words < words_for(n_samples) || (row0 >> 7) + k > gm.n_sb ||
+        k > 65535 || !d_tally)
+        return hipErrorInvalidValue;
+    const dim3 grid((gm.P + kFillStrips - 1) / kFillStrips, (uint32_t)k);
+    const uint4 *src = reinterpret_cast<const uint4 *>(d_src);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(rows_to_gt2x_kernel, grid, dim3(256), 0, st, d_src, src_stride_words, words_for(n_samples), n_rows,
-                       (unsigned long long *)d_units, gm.n_units, gm.n_sb, row0 >> 7);
+    if (d_map)
+        hipLaunchKernelGGL(fill_gt2x_kernel<kFillBed>, grid, dim3(256), 0, st, src, src_stride_words / 4, src_stride_words / 4,
+                           n_rows, (uint64_t)0, d_map, n_samples, (unsigned long long *)d_units, gm.n_units, gm.n_sb, row0 >> 7,
+                           d_tally);
+    else
+        hipLaunchKernelGGL(fill_gt2x_kernel<kFillRows>, grid, dim3(256), 0, st, src, src_stride_words / 4, src_stride_words / 4,
+                           n_rows, (uint64_t)0, d_map, n_samples, (unsigned long long *)d_units, gm.n_units, gm.n_sb, row0 >> 7,
+                           d_tally);
     return hipGetLastError();
 }
 
@@ -796,16 +846,17 @@ hipError_t launch_gt2x_to_rows(hipStream_t st, const void *d_units, uint64_t n_s
     return hipGetLastError();
 }
 
-hipError_t launch_gt2_to_gt2x(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
-                              uint64_t n_rows, void *d_units) {
+hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
+                                     uint64_t n_rows, void *d_units, unsigned long long *d_tally) {
     if (n_rows == 0 || n_samples == 0) return hipSuccess;
+    if (!d_tally) return hipErrorInvalidValue;
     const MxGeom gm = mx_geom(n_samples, n_rows);
     (void)hipGetLastError();
     for (uint64_t sb = 0; sb < gm.n_sb; sb += 32768) {
         const uint64_t k = std::min<uint64_t>(32768, gm.n_sb - sb);
-        hipLaunchKernelGGL(gt2_to_gt2x_kernel, dim3((uint32_t)((gm.n_units + 15) / 16), (uint32_t)k), dim3(256), 0, st,
-                           reinterpret_cast<const uint4 *>(d_src), stride_words, words_for(n_samples), (n_rows + 3) / 4,
-                           (unsigned long long *)d_units, gm.n_units, gm.n_sb, sb);
+        hipLaunchKernelGGL(fill_gt2x_kernel<kFillGt2>, dim3((gm.P + kFillStrips - 1) / kFillStrips, (uint32_t)k), dim3(256), 0, st,
+                           reinterpret_cast<const uint4 *>(d_src), stride_words, words_for(n_samples), n_rows, sb,
+                           (const uint8_t *)nullptr, n_samples, (unsigned long long *)d_units, gm.n_units, gm.n_sb, sb, d_tally);
     }
     return hipGetLastError();
 }
