@@ -234,9 +234,6 @@ struct nps_ctx {
     unsigned long long *d_sp_tally = nullptr;   // [batch]
     double *d_sp_lut = nullptr;                 // [batch][4]
     uint64_t sp_plain_cap = 0, sp_group_cap = 0, sp_tally_cap = 0, sp_lut_cap = 0;  // (elements)
-    bool mx_plan_valid = false, mx_plan_two_pass = false;
-    uint64_t mx_plan_m = 0;
-    MxPlan mx_plan_cache{};
     bool rtally_clean = false;              // d_rtally is all zero (allocation, or the last fused epilogue)
     // shape -> persistent-grid plan of the last resident run (occupancy queries are slow)
     bool plan_valid = false;
@@ -1818,6 +1815,321 @@ static int mx_special_pass(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row
     return NPS_OK;
 }
 
+// ---- nps_score_cohort_def and its three formats.  From the first launch that changes the context's sums an error leaves
+// queued work behind: the context is marked broken.
+struct RunGuard {
+    nps_ctx *c;
+    bool armed = false, ok = false;  // armed: a launch that changes the context's sums is queued
+    ~RunGuard() { if (armed && !ok) c->broken = true; }
+};
+
+// the fused kernels' tally words must be zero on entry; their epilogue (fold_kernel) leaves them so
+static int tally_ready(nps_ctx *c) {
+    if (!c->rtally_clean)
+        HIP_TRY(hipMemsetAsync(c->d_rtally, 0, sizeof(unsigned long long) * c->res_cap, c->stream));
+    c->rtally_clean = false;
+    return NPS_OK;
+}
+
+static int fused_epilogue(nps_ctx *c, const FusedPlan &plan, uint64_t n_tally) {
+    ProfScope ps(c, P_REDUCE);
+    HIP_TRY(launch_fold(c->stream, c->d_part_fused, plan.Q, plan.part_team_stride, c->n, c->d_part,
+                        c->chunks_used == 0 ? 1 : 0, c->d_rtally, n_tally, c->d_timeout, c->d_nloci + 1));
+    c->chunks_used = std::max(c->chunks_used, 1u);
+    c->rtally_clean = true;  // all words were zero before the run, [0, m_pad) are zero again
+    return NPS_OK;
+}
+
+// The single-read kernel of the row and the DS layouts, and its epilogue.  *ran = false with NPS_OK: the runtime refused the
+// cooperative grid (it would not be fully resident), nothing ran, and the caller scores the run in two reads -- only where
+// that is allowed (NPS_MODE_AUTO; never NPS_FMT_DS16), everything else fails.
+template <class Launch>
+static int single_read(nps_ctx *c, RunGuard &guard, const FusedPlan &plan, uint64_t n_tally, const char *what,
+                       bool may_fall_back, Launch launch, bool *ran) {
+    *ran = false;
+    int rc = tally_ready(c);
+    if (rc) return rc;
+    hipError_t fe;
+    {
+        ProfScope ps(c, P_FUSED);
+        fe = launch();
+    }
+    if (fe == hipSuccess) {
+        guard.armed = true;
+        *ran = true;
+        return fused_epilogue(c, plan, n_tally);
+    }
+    (void)hipGetLastError();
+    c->rtally_clean = true;  // (zeroed above, untouched)
+    if (!may_fall_back || fe != hipErrorCooperativeLaunchTooLarge)
+        return fail(NPS_E_HIP, "%s kernel launch failed: %s", what, hipGetErrorString(fe));
+    return NPS_OK;
+}
+
+// buffers of a strip run (a failed allocation leaves the context usable: nothing has been queued yet)
+static int mx_run_buffers(nps_ctx *c, const nps_cohort *co, const nps_scoredef *def, uint64_t m_pad, MxRouted *mx) {
+    const MxPlan &mxp = mx->plan;
+    int rc = grow(c, (void **)&c->d_mx_cpart, &c->mx_cpart_cap, mxp.cpart_floats, sizeof(float));
+    if (rc) return rc;
+    if (8 + 2ull * mxp.Q > c->mx_const_cap) {
+        rc = grow(c, (void **)&c->d_mx_const, &c->mx_const_cap, 8 + 2ull * mxp.Q, sizeof(double));
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_mx_const, 0, sizeof(double) * c->mx_const_cap, c->stream));
+    }
+    if (mx->route == MxRoute::InPassKeep) {  // (the cohort's kept tallies: allocated once, by whoever keeps them first)
+        nps_cohort *mco = const_cast<nps_cohort *>(co);
+        std::lock_guard<std::mutex> lk(mco->tally_mutex);
+        if (mx_tallies_alloc(mco) != hipSuccess) {
+            (void)hipGetLastError();
+            mx->route = MxRoute::InPass;  // (no room: the pass runs as it always did)
+        }
+    }
+    if (!def->special.empty()) {
+        rc = mx_special_buffers(c, def);
+        if (rc) return rc;
+    }
+    if (mxp.given) {
+        rc = grow(c, (void **)&c->d_mx_ops, &c->mx_ops_cap, m_pad, 48);
+        if (rc == NPS_OK) rc = grow(c, (void **)&c->d_mx_cblk, &c->mx_cblk_cap, m_pad / 128, sizeof(double));
+        if (rc) return rc;
+    }
+    const uint64_t need1 = (uint64_t)((mxp.P + 15) / 16) * m_pad;
+    if (need1 > c->mx_tally1_cap) {
+        rc = grow(c, (void **)&c->d_mx_tally1, &c->mx_tally1_cap, need1, sizeof(unsigned long long));
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_mx_tally1, 0, sizeof(unsigned long long) * c->mx_tally1_cap, c->stream));
+    }
+    return NPS_OK;
+}
+
+// NPS_FMT_GT2X: one pass per magnitude band of the definition (normally one) on the route mx_route chose
+static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                        const MxRouted &mx) {
+    const MxPlan &mxp = mx.plan;
+    const MxRoute route = mx.route;
+    const size_t n_bands = std::max<size_t>(1, def->mx_bands.size());  // (no bands: the definition is its one band)
+    unsigned long long *scratch_nloci = reinterpret_cast<unsigned long long *>(c->d_mx_const);  // (the 8 scratch doubles)
+    MxRun r;
+    r.d_units = co->d_data;
+    r.n_sb_cohort = gt2x_superblocks(co->n_rows);
+    r.sb0 = cohort_row0 >> 7;
+    r.n_samples = c->n;
+    r.n_rows = def->m;
+    r.prm = dev_params(c->params);
+    r.t_maxmis = maxmis_threshold(c->n, c->params.max_missing_rate);
+    r.d_tally = c->d_rtally;
+    r.d_const_sum = c->d_mx_const + 8;
+    r.d_cpart = c->d_mx_cpart;
+    r.d_timeout = c->d_timeout;
+    r.d_pre = c->d_rlut;
+    r.d_tally1 = c->d_mx_tally1;
+    r.d_tally_given = route == MxRoute::GivenKept ? co->d_mx_row_tally + cohort_row0 : c->d_rtally;
+    r.d_ops = c->d_mx_ops;
+    r.d_const_part = c->d_mx_cblk;
+    r.d_done = c->d_timeout + 17;
+    r.d_part0 = c->d_part;
+    r.d_status = c->d_nloci + 1;
+    for (size_t b = 0; b < n_bands; ++b) {  // band 0 counts nloci and writes the statistics
+        const bool banded = !def->mx_bands.empty();
+        const double bound = banded ? def->mx_bands[b].bound : def->mx_bound;
+        r.d_desc = banded ? def->mx_bands[b].d_desc : def->d_mx_desc ? def->d_mx_desc : def->d_desc;
+        // fixed-point scale: every weight of the band below 2^56 (fourteen hexadecimal digits)
+        r.F = 56;
+        if (bound > 0.0) {
+            int e2 = 0;
+            (void)std::frexp(bound, &e2);  // bound < 2^e2
+            r.F = std::min(1000, std::max(-1000, 56 - e2));
+        }
+        r.d_stats = b == 0 ? c->d_rstats : nullptr;
+        r.d_nloci = b == 0 ? c->d_nloci : scratch_nloci;
+        r.overwrite = c->chunks_used == 0 ? 1 : 0;
+        const bool keep = route == MxRoute::InPassKeep && b == 0;
+        r.d_keep = keep ? co->d_mx_row_tally : nullptr;
+        r.n_keep = keep ? (uint64_t)mxp.n_sb * 128 : 0;
+        int rc = tally_ready(c);
+        if (rc) return rc;
+        if (route == MxRoute::GivenTallied) {
+            ProfScope ps(c, P_TALLY);
+            HIP_TRY(launch_mx_tally(c->stream, mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally));
+        }
+        hipError_t fe;
+        {
+            ProfScope ps(c, mxp.given ? P_ACCUM : P_FUSED);
+            fe = mxp.given ? launch_mx_given(c->stream, mxp, r) : launch_fused_mx(c->stream, mxp, r);
+        }
+        if (fe != hipSuccess) {
+            (void)hipGetLastError();  // the runtime refused the cooperative grid: nothing ran
+            c->rtally_clean = route != MxRoute::GivenTallied;
+            return fail(NPS_E_HIP, "NPS_FMT_GT2X kernel launch failed: %s", hipGetErrorString(fe));
+        }
+        guard.armed = true;
+        {
+            ProfScope ps(c, P_REDUCE);
+            HIP_TRY(launch_mx_fold(c->stream, mxp, r));
+            HIP_TRY(hipMemsetAsync(r.d_const_sum, 0, sizeof(double) * 2 * mxp.Q, c->stream));
+        }
+        c->chunks_used = std::max(c->chunks_used, 1u);
+        c->rtally_clean = true;
+    }
+    if (!def->special.empty()) {
+        int rc = mx_special_pass(c, co, cohort_row0, def, scratch_nloci);
+        if (rc) return rc;
+    }
+    if (route == MxRoute::InPassKeep) {
+        // the kept tallies are published only once they ARE in device memory (another context may score this cohort
+        // from another thread and stream): one wait, on the cohort's first pass only
+        // (a superblock that was valid before -- rows uploaded, then others rewritten by the generator -- has received the
+        //  same words again: a reader on another thread sees complete words at every moment)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        nps_cohort *mco = const_cast<nps_cohort *>(co);
+        std::lock_guard<std::mutex> lk(mco->tally_mutex);
+        mx_tallies_mark(mco, 0, gt2x_superblocks(co->n_rows), true);
+        mco->mx_tally_asked.store(true, std::memory_order_release);
+    }
+    return NPS_OK;
+}
+
+// NPS_FMT_DS32 / NPS_FMT_DS16: the single-read kernel (plan.ok), else -- float32 rows only -- tally, params, accumulate
+static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                        int mode, const FusedPlan &plan, uint64_t n_tally) {
+    const uint64_t m = def->m;
+    const bool is_ds16 = co->format == NPS_FMT_DS16;
+    const uint64_t stride_f = co->stride_bytes / 4;  // (NPS_FMT_DS32 only below the fused branch)
+    const float *ds = (const float *)((const char *)co->d_data + cohort_row0 * co->stride_bytes);
+    if (plan.ok && c->n) {
+        bool ran = false;
+        int rc = single_read(c, guard, plan, n_tally, "fused DS", mode == NPS_MODE_AUTO && !is_ds16, [&]() {
+            return launch_ds_fused(c->stream, plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc,
+                                   dev_params(c->params), maxmis_threshold(c->n, c->params.max_missing_rate), c->d_rtally,
+                                   c->d_rstats, c->d_nloci, c->d_part_fused, c->d_timeout);
+        }, &ran);
+        if (rc || ran) return rc;
+    }
+    if (is_ds16) return fail(NPS_E_UNSUPPORTED, "NPS_FMT_DS16 cohorts are scored by the single-read kernel only");
+    // launches of >= 2048 rows keep every CU busy in both kernels (one workgroup per row in the
+    // tally; samples x row chunks in the accumulation)
+    uint64_t block_rows = env_u64("NPS_BLOCK_ROWS", 0);
+    if (block_rows == 0) block_rows = std::max<uint64_t>(2048, (256ull << 20) / co->stride_bytes);
+    int rc = ensure_all_chunks(c);
+    if (rc) return rc;
+    guard.armed = true;
+    for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
+        const uint64_t k = std::min(block_rows, m - r0);
+        {
+            ProfScope ps(c, P_TALLY);
+            HIP_TRY(launch_ds_tally(c->stream, ds + r0 * stride_f, stride_f, c->n, def->d_desc + r0,
+                                    k, c->d_rds_tally + r0));
+        }
+        {
+            ProfScope ps(c, P_PARAMS);
+            HIP_TRY(launch_ds_params(c->stream, c->d_rds_tally + r0, def->d_desc + r0, k, c->n,
+                                     dev_params(c->params), c->d_rds_rowp + r0, c->d_rstats + r0,
+                                     c->d_nloci));
+        }
+        {
+            ProfScope ps(c, P_ACCUM);
+            HIP_TRY(launch_ds_accumulate(c->stream, ds + r0 * stride_f, stride_f, c->n,
+                                         c->d_rds_rowp + r0, k, c->d_part, c->n_chunks,
+                                         c->geom.part_chunk_stride));
+        }
+    }
+    return NPS_OK;
+}
+
+// NPS_FMT_GT2: the single-read kernel (plan.ok), else per block of rows tally, params, accumulate
+static int score_run_gt2(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                         int mode, const FusedPlan &plan, uint64_t n_tally) {
+    const uint64_t m = def->m;
+    const uint64_t stride_words = co->stride_bytes / 4;
+    const uint32_t *codes = (const uint32_t *)co->d_data + (cohort_row0 >> 2) * stride_words * 4;
+    const nps_row_desc *d_desc = def->d_desc;
+    const int parity = co->optimized ? 1 : 0;  // the kernels undo the parity layout for the tally
+    if (plan.ok && c->n) {
+        bool ran = false;
+        int rc = single_read(c, guard, plan, n_tally, "fused", mode == NPS_MODE_AUTO, [&]() {
+            return launch_fused(c->stream, plan, codes, stride_words, c->n, m, d_desc, dev_params(c->params), c->d_rtally,
+                                c->d_rstats, c->d_nloci, c->d_part_fused, c->d_timeout, parity);
+        }, &ran);
+#ifdef NPS_DIAGNOSTICS
+        if (rc == NPS_OK && ran && getenv("NPS_TELEMETRY")) {  // diagnostics of the control wave (cycles, summed)
+            unsigned long long t[8] = {0};
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipMemcpy(t, (char *)c->d_timeout + 16, sizeof t, hipMemcpyDeviceToHost);
+            (void)hipMemset((char *)c->d_timeout + 16, 0, sizeof t);
+            const double wg = (double)plan.P * plan.Q, st = t[4] ? (double)t[4] : 1.0;
+            fprintf(stderr, "[nps] fused P=%u Q=%u T=%u: per step per WG: spins %.2f, poll wait "
+                    "%.0f cyc, control chain %.0f cyc, barrier wait %.0f cyc (steps/WG %.0f)\n",
+                    plan.P, plan.Q, plan.threads, t[0] / st, t[1] / st, t[2] / st, t[3] / st, st / wg);
+        }
+#endif
+        if (rc || ran) return rc;
+    }
+    // rows per tally/accumulate pair; default ~96 MB so the second read can hit the 256 MB
+    // Infinity Cache
+    uint64_t block_rows = env_u64("NPS_BLOCK_ROWS", 0);
+    if (block_rows == 0) block_rows = std::max<uint64_t>(64, (96ull << 20) / co->stride_bytes);
+    block_rows = (block_rows + 15) / 16 * 16;
+    int rc = ensure_all_chunks(c);
+    if (rc) return rc;
+    guard.armed = true;
+    c->rtally_clean = false;  // the two-pass tally kernel leaves its counts in d_rtally
+    for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
+        const uint64_t k = std::min(block_rows, m - r0);
+        const uint64_t k_pad = (k + 3) / 4 * 4;  // only the last block can be ragged
+        {
+            ProfScope ps(c, P_TALLY);
+            HIP_TRY(launch_tally_packed(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words,
+                                        c->n, k, c->d_rtally + r0, parity));
+        }
+        {
+            ProfScope ps(c, P_PARAMS);
+            HIP_TRY(launch_row_params(c->stream, c->d_rtally + r0, d_desc + r0, k, k_pad, c->n,
+                                      dev_params(c->params), c->d_rlut + r0 * 4, c->d_rstats + r0,
+                                      c->d_nloci));
+        }
+        if (c->n) {
+            AccumGeom g = c->geom;
+            const uint32_t groups = (uint32_t)(k_pad / 4);
+            g.groups_per_chunk = std::max(1u, (groups + g.n_chunks - 1) / g.n_chunks);
+            ProfScope ps(c, P_ACCUM);
+            HIP_TRY(launch_accumulate(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words, k,
+                                      c->d_rlut + r0 * 4, g, c->d_part, parity));
+        }
+    }
+    return NPS_OK;
+}
+
+// the single-read plan of a row-layout or DS run (cached on the context), and what refuses it before anything changes
+static int fused_plan_for_run(nps_ctx *c, const nps_cohort *co, uint64_t m, int mode, FusedPlan *plan) {
+    const bool is_ds16 = co->format == NPS_FMT_DS16, is_ds = co->format == NPS_FMT_DS32 || is_ds16;
+    if (c->plan_valid && c->plan_fmt == co->format && c->plan_m == m) {
+        *plan = c->plan_cache;
+    } else {
+        const int want = (int)env_u64("NPS_FUSED_THREADS", 0), max_q = (int)env_u64("NPS_FUSED_MAXQ", 0);
+        if (is_ds)
+            HIP_TRY(ds_fused_plan(c->device, c->n, m, want, max_q, plan, is_ds16 ? 2 : 4));
+        else
+            HIP_TRY(fused_plan(c->device, c->n, m, want, max_q, plan));
+        c->plan_cache = *plan;
+        c->plan_fmt = co->format;
+        c->plan_m = m;
+        c->plan_valid = true;
+    }
+    if (env_u64("NPS_DISABLE_FUSED", 0) == 1 && mode == NPS_MODE_AUTO) plan->ok = false;
+    if (is_ds && co->ds_bad_rows) {  // a dosage outside [0, 2] somewhere in the cohort: the two-pass kernels take any value
+        if (mode == NPS_MODE_FUSED)
+            return fail(NPS_E_INVAL, "%llu row(s) of the cohort hold FORMAT/DS values outside [0, 2]: the single-read DS "
+                        "kernel hands dosage sums over in fixed point and needs that range (NPS_MODE_AUTO / "
+                        "NPS_MODE_TWOPASS score such a cohort in two reads)", (unsigned long long)co->ds_bad_rows);
+        plan->ok = false;
+    }
+    if (!plan->ok && (mode == NPS_MODE_FUSED || is_ds16))
+        return fail(NPS_E_UNSUPPORTED, "shape (%llu samples, %llu rows) does not fit the fused "
+                    "persistent grid%s", (unsigned long long)c->n, (unsigned long long)m,
+                    is_ds16 ? " (NPS_FMT_DS16 has no two-read kernels: use NPS_FMT_DS32)" : "");
+    return NPS_OK;
+}
+
 // Everything that can be refused is checked BEFORE the context changes: a call that returns an error
 // from its validation leaves the context exactly as it was, so it can be repeated (e.g. in another
 // mode).  The rows without genotype data are applied, and the run is registered for nps_flush, only
@@ -1852,107 +2164,41 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
     if (!is_ds && (cohort_row0 & 3))
         return fail(NPS_E_INVAL, "cohort_row0 must be a multiple of 4 (rows are stored in groups of 4)");
     HIP_TRY(hipSetDevice(c->device));
-    MxPlan mxp;
-    bool kept_tallies = false, harvest = false;
+    MxRouted mx;  // NPS_FMT_GT2X: which kernel scores the run, where its row tallies come from, and the plan (nps_mx_route.h)
     if (is_mx && m && c->n) {
-        // A run whose superblocks all carry their tallies is scored with them given under NPS_MODE_AUTO -- the "two-pass" plan
-        // (independent workgroups) without its tally pass -- when the tallies were asked for (nps_cohort_keep_tallies, a pass
-        // that kept them: any size), or when they came with the rows (upload, upload_bed, convert) and a strip has ONE row
-        // team: only there is the given-tallies kernel faster than the pass that counts them (`one_team` below).  Smaller
-        // cohorts keep and serve their write-time tallies (nps_cohort_row_tallies) and are scored in the pass.
-        const bool run_valid = mode == NPS_MODE_AUTO && mx_tallies_valid(co, cohort_row0 >> 7, (m + 127) / 128);
-        if (run_valid) {
-            kept_tallies = co->mx_tally_asked.load(std::memory_order_acquire);
-            if (!kept_tallies) {
-                MxPlan p1;
-                HIP_TRY(mx_plan(c->device, c->n, m, false, &p1));
-                kept_tallies = p1.ok && (p1.given || p1.Q == 1);
-            }
-        }
-        if (!run_valid && mode == NPS_MODE_AUTO) {
-            // Does the single-read kernel's resident grid cover the chip at this size, and will the cohort be scored again?
-            //   * a resident grid exists (P <= compute units) and the run covers the whole cohort: the pass counts the tallies
-            //     anyway -- where later passes want them given (the grid covers less than nine tenths of the chip, or the
-            //     caller said nps_cohort_expect_passes >= 2) its epilogue KEEPS them with the cohort (`harvest`): the first
-            //     run is one read, every later one runs with the tallies given (round 6; until then the first run of such
-            //     a size was a tally pass + a given-tallies pass: two reads);
-            //   * no resident grid (more strips than compute units), or a partial run of at least a quarter of the cohort:
-            //     count the cohort's tallies once (one more read) and keep them (the cohort's own cache: rewriting rows
-            //     drops it); shorter runs tally just their own rows (two reads of those rows).
-            MxPlan p1;
-            HIP_TRY(mx_plan(c->device, c->n, m, false, &p1));
-            int cus = 0;
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            // (nine tenths, by measurement: at 400 000 samples -- 196 strips, 77 % of the chip -- the in-pass kernel runs at
-            //  0.64-0.67 of the roofline and the same cohort with its tallies given at 0.73-0.75; until round 6, when keeping
-            //  the tallies still cost a pass of its own, the line was drawn at seven tenths)
-            const bool covers = p1.ok && !p1.given && (uint64_t)p1.P * p1.Q * 10 >= (uint64_t)cus * 9;
-            // (only where a strip has ONE row team -- more than 128 strips, 262 144 samples: with several teams per strip the
-            //  given-tallies kernel is no faster than the pass that counts them -- 250 000 samples 11.3 against 11.4 ms,
-            //  200 000 equal -- and slower below: 100 000 samples 5.05 against 4.27 ms, profiles/r06_harvest.txt)
-            const bool one_team = p1.ok && (p1.given || p1.Q == 1);
-            const bool want_kept = one_team && (!covers || co->expect_passes.load(std::memory_order_relaxed) >= 2);
-            const bool whole = cohort_row0 == 0 && m == co->n_rows;
-            if (p1.ok && want_kept) {
-                if (!p1.given && whole && m >= 1024) {
-                    harvest = true;
-                } else if ((p1.given || (!covers && m >= 16384)) && m * 4 >= co->n_rows) {
-                    nps_cohort *mco = const_cast<nps_cohort *>(co);
-                    std::lock_guard<std::mutex> lk(mco->tally_mutex);
-                    rc = mx_keep_tallies_locked(mco);  // (counts what is not valid yet: nothing, if another thread was first)
-                    if (rc) return rc;
-                    HIP_TRY(hipSetDevice(c->device));
-                    kept_tallies = true;
-                }
-            }
-        }
-        const bool two_pass = mode == NPS_MODE_TWOPASS || kept_tallies;
-        if (c->mx_plan_valid && c->mx_plan_m == m && c->mx_plan_two_pass == two_pass) {
-            mxp = c->mx_plan_cache;
-        } else {
-            HIP_TRY(mx_plan(c->device, c->n, m, two_pass, &mxp));
-            c->mx_plan_cache = mxp;
-            c->mx_plan_m = m;
-            c->mx_plan_two_pass = two_pass;
-            c->mx_plan_valid = true;
-        }
-        if (!mxp.ok)
+        MxRouteIn in;
+        in.mode = mode;
+        HIP_TRY(mx_cus(c->device, &in.cus));
+        in.n_samples = c->n;
+        in.m = m;
+        in.n_rows_cohort = co->n_rows;
+        in.cohort_row0 = cohort_row0;
+        in.run_tallies_valid = mx_tallies_valid(co, cohort_row0 >> 7, (m + 127) / 128);
+        in.tallies_asked = co->mx_tally_asked.load(std::memory_order_acquire);
+        in.expect_passes = co->expect_passes.load(std::memory_order_relaxed);
+        mx = mx_route(in);
+        if (!mx.ok)
             return fail(NPS_E_UNSUPPORTED, "shape (%llu samples, %llu rows) is beyond the NPS_FMT_GT2X kernels (2^27 samples)",
                         (unsigned long long)c->n, (unsigned long long)m);
-        // more strips than compute units: the single-read kernel cannot hold the grid resident; AUTO takes the
-        // tally + accumulate pair (two reads), an explicit NPS_MODE_FUSED is refused
-        if (mxp.given && mode == NPS_MODE_FUSED)
+        if (mx.refused_fused)
             return fail(NPS_E_UNSUPPORTED, "shape (%llu samples, %llu rows) does not fit the persistent grid of the "
                         "single-read NPS_FMT_GT2X kernel (one 2048-sample strip per compute unit); NPS_MODE_AUTO "
                         "scores it in two reads", (unsigned long long)c->n, (unsigned long long)m);
+        if (mx.count_cohort_first) {
+            nps_cohort *mco = const_cast<nps_cohort *>(co);
+            std::lock_guard<std::mutex> lk(mco->tally_mutex);
+            rc = mx_keep_tallies_locked(mco);  // (counts what is not valid yet: nothing, if another thread was first)
+            if (rc) return rc;
+            HIP_TRY(hipSetDevice(c->device));
+        }
+#ifdef NPS_DIAGNOSTICS
+        if (getenv("NPS_MXG_Q")) HIP_TRY(mx_plan(c->device, c->n, m, mx.plan.given, &mx.plan));  // (mx_plan's override)
+#endif
     }
     FusedPlan plan;
     if (!is_mx && mode != NPS_MODE_TWOPASS && m && c->n) {
-        if (c->plan_valid && c->plan_fmt == co->format && c->plan_m == m) {
-            plan = c->plan_cache;
-        } else {
-            const int want = (int)env_u64("NPS_FUSED_THREADS", 0), max_q = (int)env_u64("NPS_FUSED_MAXQ", 0);
-            if (is_ds)
-                HIP_TRY(ds_fused_plan(c->device, c->n, m, want, max_q, &plan, is_ds16 ? 2 : 4));
-            else
-                HIP_TRY(fused_plan(c->device, c->n, m, want, max_q, &plan));
-            c->plan_cache = plan;
-            c->plan_fmt = co->format;
-            c->plan_m = m;
-            c->plan_valid = true;
-        }
-        if (env_u64("NPS_DISABLE_FUSED", 0) == 1 && mode == NPS_MODE_AUTO) plan.ok = false;
-        if (is_ds && co->ds_bad_rows) {  // a dosage outside [0, 2] somewhere in the cohort: the two-pass kernels take any value
-            if (mode == NPS_MODE_FUSED)
-                return fail(NPS_E_INVAL, "%llu row(s) of the cohort hold FORMAT/DS values outside [0, 2]: the single-read DS "
-                            "kernel hands dosage sums over in fixed point and needs that range (NPS_MODE_AUTO / "
-                            "NPS_MODE_TWOPASS score such a cohort in two reads)", (unsigned long long)co->ds_bad_rows);
-            plan.ok = false;
-        }
-        if (!plan.ok && (mode == NPS_MODE_FUSED || is_ds16))
-            return fail(NPS_E_UNSUPPORTED, "shape (%llu samples, %llu rows) does not fit the fused "
-                        "persistent grid%s", (unsigned long long)c->n, (unsigned long long)m,
-                        is_ds16 ? " (NPS_FMT_DS16 has no two-read kernels: use NPS_FMT_DS32)" : "");
+        rc = fused_plan_for_run(c, co, m, mode, &plan);
+        if (rc) return rc;
     }
 
     rc = run_batch(c);  // keep push order: finish whatever was streamed before
@@ -1986,289 +2232,34 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
     rc = ensure_resident_buffers(c, n_tally);
     if (rc) return rc;
     if (is_mx && c->n) {
-        rc = grow(c, (void **)&c->d_mx_cpart, &c->mx_cpart_cap, mxp.cpart_floats, sizeof(float));
+        rc = mx_run_buffers(c, co, def, m_pad, &mx);
         if (rc) return rc;
-        if (8 + 2ull * mxp.Q > c->mx_const_cap) {
-            rc = grow(c, (void **)&c->d_mx_const, &c->mx_const_cap, 8 + 2ull * mxp.Q, sizeof(double));
-            if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(c->d_mx_const, 0, sizeof(double) * c->mx_const_cap, c->stream));
-        }
-        if (harvest) {  // (the cohort's kept tallies: allocated once, by whoever harvests first)
-            nps_cohort *mco = const_cast<nps_cohort *>(co);
-            std::lock_guard<std::mutex> lk(mco->tally_mutex);
-            if (mx_tallies_alloc(mco) != hipSuccess) {
-                (void)hipGetLastError();
-                harvest = false;  // (no room: the pass runs as it always did)
-            }
-        }
-        if (!def->special.empty()) {
-            rc = mx_special_buffers(c, def);
-            if (rc) return rc;
-        }
-        if (mxp.given) {
-            rc = grow(c, (void **)&c->d_mx_ops, &c->mx_ops_cap, m_pad, 48);
-            if (rc == NPS_OK) rc = grow(c, (void **)&c->d_mx_cblk, &c->mx_cblk_cap, m_pad / 128, sizeof(double));
-            if (rc) return rc;
-        }
-        const uint64_t need1 = (uint64_t)((mxp.P + 15) / 16) * m_pad;
-        if (need1 > c->mx_tally1_cap) {
-            rc = grow(c, (void **)&c->d_mx_tally1, &c->mx_tally1_cap, need1, sizeof(unsigned long long));
-            if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(c->d_mx_tally1, 0, sizeof(unsigned long long) * c->mx_tally1_cap, c->stream));
-        }
     }
     if (fused) {
         rc = grow(c, (void **)&c->d_part_fused, &c->part_fused_cap,
                   (uint64_t)plan.Q * plan.part_team_stride, sizeof(double));
         if (rc) return rc;
     }
-    if (is_ds) {
-        if (m_pad > c->res_ds_cap) {
-            uint64_t cap_a = c->res_ds_cap, cap_b = c->res_ds_cap;
-            rc = grow(c, (void **)&c->d_rds_tally, &cap_a, m_pad, sizeof(DsTally));
-            if (rc == NPS_OK) rc = grow(c, (void **)&c->d_rds_rowp, &cap_b, m_pad, sizeof(DsRowP));
-            c->res_ds_cap = std::min(cap_a, cap_b);
-            if (rc) return rc;
-        }
-    }
-
-    // ---- launches.  From here on an error leaves queued work behind: the context is marked broken.
-    struct Guard {
-        nps_ctx *c;
-        bool armed = false, ok = false;  // armed: a launch that changes the context's sums is queued
-        ~Guard() { if (armed && !ok) c->broken = true; }
-    } guard{c};
-    auto done = [&]() {
-        commit();
-        guard.ok = true;
-        return NPS_OK;
-    };
-    // the fused kernels' tally words must be zero on entry; their epilogue (fold_kernel) leaves them so
-    auto tally_ready = [&]() -> int {
-        if (!c->rtally_clean)
-            HIP_TRY(hipMemsetAsync(c->d_rtally, 0, sizeof(unsigned long long) * c->res_cap, c->stream));
-        c->rtally_clean = false;
-        return NPS_OK;
-    };
-    auto epilogue = [&]() -> int {
-        ProfScope ps(c, P_REDUCE);
-        HIP_TRY(launch_fold(c->stream, c->d_part_fused, plan.Q, plan.part_team_stride, c->n, c->d_part,
-                            c->chunks_used == 0 ? 1 : 0, c->d_rtally, n_tally, c->d_timeout,
-                            c->d_nloci + 1));
-        c->chunks_used = std::max(c->chunks_used, 1u);
-        c->rtally_clean = true;  // all words were zero before the run, [0, m_pad) are zero again
-        return NPS_OK;
-    };
-
-    if (is_mx) {
-        if (c->n == 0) return done();
-        const int64_t t_maxmis = maxmis_threshold(c->n, c->params.max_missing_rate);
-        // one pass per magnitude band of the definition (normally one): band 0 counts nloci and writes the statistics
-        struct Run {
-            const nps_row_desc *d_desc;
-            double bound;
-        };
-        std::vector<Run> runs;
-        if (def->mx_bands.empty())
-            runs.push_back(Run{def->d_mx_desc ? def->d_mx_desc : def->d_desc, def->mx_bound});
-        else
-            for (const auto &mb : def->mx_bands) runs.push_back(Run{mb.d_desc, mb.bound});
-        unsigned long long *scratch_nloci = reinterpret_cast<unsigned long long *>(c->d_mx_const);  // (the 8 scratch doubles)
-        double *const_slots = c->d_mx_const + 8;
-        for (size_t b = 0; b < runs.size(); ++b) {
-            // fixed-point scale: every weight of the band below 2^56 (fourteen hexadecimal digits)
-            int F = 56;
-            if (runs[b].bound > 0.0) {
-                int e2 = 0;
-                (void)std::frexp(runs[b].bound, &e2);  // bound < 2^e2
-                F = std::min(1000, std::max(-1000, 56 - e2));
-            }
-            rc = tally_ready();
-            if (rc) return rc;
-            if (mxp.given && !kept_tallies) {
-                ProfScope ps(c, P_TALLY);
-                HIP_TRY(launch_mx_tally(c->stream, mxp, co->d_data, gt2x_superblocks(co->n_rows), cohort_row0 >> 7, c->n,
-                                        c->d_rtally));
-            }
-            hipError_t fe;
-            {
-                ProfScope ps(c, mxp.given ? P_ACCUM : P_FUSED);
-                if (mxp.given)
-                    fe = launch_mx_given(c->stream, mxp, co->d_data, gt2x_superblocks(co->n_rows), cohort_row0 >> 7, c->n, m,
-                                         runs[b].d_desc, dev_params(c->params), t_maxmis, F,
-                                         kept_tallies ? co->d_mx_row_tally + cohort_row0 : c->d_rtally,
-                                         b == 0 ? c->d_rstats : nullptr, b == 0 ? c->d_nloci : scratch_nloci, const_slots,
-                                         c->d_mx_cpart, c->d_mx_ops, c->d_mx_cblk, c->d_timeout + 17, c->d_timeout);
-                else
-                    fe = launch_fused_mx(c->stream, mxp, co->d_data, gt2x_superblocks(co->n_rows), cohort_row0 >> 7, c->n, m,
-                                         runs[b].d_desc, dev_params(c->params), t_maxmis, F, c->d_rlut,
-                                         kept_tallies ? co->d_mx_row_tally + cohort_row0 : c->d_rtally, c->d_mx_tally1,
-                                         b == 0 ? c->d_rstats : nullptr, b == 0 ? c->d_nloci : scratch_nloci,
-                                         const_slots, c->d_mx_cpart, c->d_timeout);
-            }
-            if (fe != hipSuccess) {
-                (void)hipGetLastError();  // the runtime refused the cooperative grid: nothing ran
-                c->rtally_clean = !mxp.given || kept_tallies;
-                return fail(NPS_E_HIP, "NPS_FMT_GT2X kernel launch failed: %s", hipGetErrorString(fe));
-            }
-            guard.armed = true;
-            {
-                ProfScope ps(c, P_REDUCE);
-                HIP_TRY(launch_mx_fold(c->stream, mxp, c->d_mx_cpart, c->n, F, const_slots, c->d_part,
-                                       c->chunks_used == 0 ? 1 : 0, c->d_rtally, m_pad, c->d_mx_tally1,
-                                       (uint64_t)((mxp.P + 15) / 16) * m_pad, c->d_timeout, c->d_nloci + 1,
-                                       !mxp.given && mxp.U < 64 /* launch_fused_mx cut its own strips */,
-                                       harvest && b == 0 && !mxp.given ? co->d_mx_row_tally : nullptr,
-                                       harvest && b == 0 && !mxp.given ? m_pad : 0));
-                HIP_TRY(hipMemsetAsync(const_slots, 0, sizeof(double) * 2 * mxp.Q, c->stream));
-            }
-            c->chunks_used = std::max(c->chunks_used, 1u);
-            c->rtally_clean = true;
-        }
-        if (!def->special.empty()) {
-            rc = mx_special_pass(c, co, cohort_row0, def, scratch_nloci);
-            if (rc) return rc;
-        }
-        if (harvest && !mxp.given) {
-            // the kept tallies are published only once they ARE in device memory (another context may score this cohort
-            // from another thread and stream): one wait, on the cohort's first pass only
-            // (a superblock that was valid before -- rows uploaded, then others rewritten by the generator -- has received the
-            //  same words again: a reader on another thread sees complete words at every moment)
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            nps_cohort *mco = const_cast<nps_cohort *>(co);
-            std::lock_guard<std::mutex> lk(mco->tally_mutex);
-            mx_tallies_mark(mco, 0, gt2x_superblocks(co->n_rows), true);
-            mco->mx_tally_asked.store(true, std::memory_order_release);
-        }
-        return done();
-    }
-
-    if (is_ds) {
-        const uint64_t stride_f = co->stride_bytes / 4;  // (NPS_FMT_DS32 only below the fused branch)
-        const float *ds = (const float *)((const char *)co->d_data + cohort_row0 * co->stride_bytes);
-        if (fused) {
-            rc = tally_ready();
-            if (rc) return rc;
-            hipError_t fe;
-            {
-                ProfScope ps(c, P_FUSED);
-                fe = launch_ds_fused(c->stream, plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc,
-                                     dev_params(c->params), maxmis_threshold(c->n, c->params.max_missing_rate), c->d_rtally, c->d_rstats,
-                                     c->d_nloci, c->d_part_fused, c->d_timeout);
-            }
-            if (fe == hipSuccess) {
-                guard.armed = true;
-                rc = epilogue();
-                if (rc) return rc;
-                return done();
-            }
-            (void)hipGetLastError();  // the runtime refused the cooperative grid: nothing ran
-            c->rtally_clean = true;   // (zeroed above, untouched)
-            if (mode == NPS_MODE_FUSED || is_ds16 || fe != hipErrorCooperativeLaunchTooLarge)
-                return fail(NPS_E_HIP, "fused DS kernel launch failed: %s", hipGetErrorString(fe));
-        }
-        if (is_ds16) return fail(NPS_E_UNSUPPORTED, "NPS_FMT_DS16 cohorts are scored by the single-read kernel only");
-        // launches of >= 2048 rows keep every CU busy in both kernels (one workgroup per row in the
-        // tally; samples x row chunks in the accumulation)
-        uint64_t block_rows = env_u64("NPS_BLOCK_ROWS", 0);
-        if (block_rows == 0) block_rows = std::max<uint64_t>(2048, (256ull << 20) / co->stride_bytes);
-        rc = ensure_all_chunks(c);
+    if (is_ds && m_pad > c->res_ds_cap) {
+        uint64_t cap_a = c->res_ds_cap, cap_b = c->res_ds_cap;
+        rc = grow(c, (void **)&c->d_rds_tally, &cap_a, m_pad, sizeof(DsTally));
+        if (rc == NPS_OK) rc = grow(c, (void **)&c->d_rds_rowp, &cap_b, m_pad, sizeof(DsRowP));
+        c->res_ds_cap = std::min(cap_a, cap_b);
         if (rc) return rc;
-        guard.armed = true;
-        for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
-            const uint64_t k = std::min(block_rows, m - r0);
-            {
-                ProfScope ps(c, P_TALLY);
-                HIP_TRY(launch_ds_tally(c->stream, ds + r0 * stride_f, stride_f, c->n, def->d_desc + r0,
-                                        k, c->d_rds_tally + r0));
-            }
-            {
-                ProfScope ps(c, P_PARAMS);
-                HIP_TRY(launch_ds_params(c->stream, c->d_rds_tally + r0, def->d_desc + r0, k, c->n,
-                                         dev_params(c->params), c->d_rds_rowp + r0, c->d_rstats + r0,
-                                         c->d_nloci));
-            }
-            {
-                ProfScope ps(c, P_ACCUM);
-                HIP_TRY(launch_ds_accumulate(c->stream, ds + r0 * stride_f, stride_f, c->n,
-                                             c->d_rds_rowp + r0, k, c->d_part, c->n_chunks,
-                                             c->geom.part_chunk_stride));
-            }
-        }
-        return done();
     }
 
-    const uint64_t stride_words = co->stride_bytes / 4;
-    const uint32_t *codes = (const uint32_t *)co->d_data + (cohort_row0 >> 2) * stride_words * 4;
-    const nps_row_desc *d_desc = def->d_desc;
-    const int parity = co->optimized ? 1 : 0;  // the kernels undo the parity layout for the tally
-    if (fused) {
-        rc = tally_ready();
-        if (rc) return rc;
-        hipError_t fe;
-        {
-            ProfScope ps(c, P_FUSED);
-            fe = launch_fused(c->stream, plan, codes, stride_words, c->n, m, d_desc,
-                              dev_params(c->params), c->d_rtally, c->d_rstats, c->d_nloci,
-                              c->d_part_fused, c->d_timeout, parity);
-        }
-        if (fe == hipSuccess) {
-            guard.armed = true;
-            rc = epilogue();
-            if (rc) return rc;
-#ifdef NPS_DIAGNOSTICS
-            if (getenv("NPS_TELEMETRY")) {  // diagnostics of the control wave (cycles, summed)
-                unsigned long long t[8] = {0};
-                (void)hipStreamSynchronize(c->stream);
-                (void)hipMemcpy(t, (char *)c->d_timeout + 16, sizeof t, hipMemcpyDeviceToHost);
-                (void)hipMemset((char *)c->d_timeout + 16, 0, sizeof t);
-                const double wg = (double)plan.P * plan.Q, st = t[4] ? (double)t[4] : 1.0;
-                fprintf(stderr, "[nps] fused P=%u Q=%u T=%u: per step per WG: spins %.2f, poll wait "
-                        "%.0f cyc, control chain %.0f cyc, barrier wait %.0f cyc (steps/WG %.0f)\n",
-                        plan.P, plan.Q, plan.threads, t[0] / st, t[1] / st, t[2] / st, t[3] / st, st / wg);
-            }
-#endif
-            return done();
-        }
-        // the runtime refused the cooperative grid (it would not be fully resident): nothing ran
-        (void)hipGetLastError();
-        c->rtally_clean = true;
-        if (mode == NPS_MODE_FUSED || fe != hipErrorCooperativeLaunchTooLarge)
-            return fail(NPS_E_HIP, "fused kernel launch failed: %s", hipGetErrorString(fe));
-    }
-    // rows per tally/accumulate pair; default ~96 MB so the second read can hit the 256 MB
-    // Infinity Cache
-    uint64_t block_rows = env_u64("NPS_BLOCK_ROWS", 0);
-    if (block_rows == 0) block_rows = std::max<uint64_t>(64, (96ull << 20) / co->stride_bytes);
-    block_rows = (block_rows + 15) / 16 * 16;
-    rc = ensure_all_chunks(c);
+    // ---- launches
+    RunGuard guard{c};
+    if (is_mx)
+        rc = c->n ? score_run_mx(c, guard, co, cohort_row0, def, mx) : NPS_OK;
+    else if (is_ds)
+        rc = score_run_ds(c, guard, co, cohort_row0, def, mode, plan, n_tally);
+    else
+        rc = score_run_gt2(c, guard, co, cohort_row0, def, mode, plan, n_tally);
     if (rc) return rc;
-    guard.armed = true;
-    c->rtally_clean = false;  // the two-pass tally kernel leaves its counts in d_rtally
-    for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
-        const uint64_t k = std::min(block_rows, m - r0);
-        const uint64_t k_pad = (k + 3) / 4 * 4;  // only the last block can be ragged
-        {
-            ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_packed(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words,
-                                        c->n, k, c->d_rtally + r0, parity));
-        }
-        {
-            ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_row_params(c->stream, c->d_rtally + r0, d_desc + r0, k, k_pad, c->n,
-                                      dev_params(c->params), c->d_rlut + r0 * 4, c->d_rstats + r0,
-                                      c->d_nloci));
-        }
-        if (c->n) {
-            AccumGeom g = c->geom;
-            const uint32_t groups = (uint32_t)(k_pad / 4);
-            g.groups_per_chunk = std::max(1u, (groups + g.n_chunks - 1) / g.n_chunks);
-            ProfScope ps(c, P_ACCUM);
-            HIP_TRY(launch_accumulate(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words, k,
-                                      c->d_rlut + r0 * 4, g, c->d_part, parity));
-        }
-    }
-    return done();
+    commit();
+    guard.ok = true;
+    return NPS_OK;
 }
 
 extern "C" int nps_score_cohort(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0,
@@ -2780,10 +2771,9 @@ extern "C" int nps_fused_geometry(nps_ctx *c, int format, uint64_t n_rows, uint3
         //  the tally pass; its slices are still the 2048-sample strips)
         if (mp.ok && mp.given) HIP_TRY(mx_plan(c->device, c->n, n_rows, true, &mp));
         // (the single-read kernel may cut its own strips of 62 units = 1 984 samples from the unit sequence: what the grid IS)
-        const bool vs = mp.ok && !mp.given && mp.U < 64;
-        if (slices) *slices = mp.ok ? (vs ? mp.Pv : mp.P) : 0;
+        if (slices) *slices = mp.ok ? mp.grid_P : 0;
         if (teams) *teams = mp.ok ? mp.Q : 0;
-        if (samples_per_slice) *samples_per_slice = mp.ok ? (vs ? 32 * mp.U : 2048) : 0;
+        if (samples_per_slice) *samples_per_slice = mp.ok ? 32 * mp.grid_U : 0;
         return NPS_OK;
     }
     FusedPlan plan;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/nps.h"
+#include "nps_mx_route.h"
 
 namespace nps {
 
@@ -266,21 +267,7 @@ hipError_t launch_multi_finish(hipStream_t st, const double *d_part, uint64_t n_
                                const double *d_offsets, int have_sums, double *d_scores, int normalise = 1);
 
 // ---- single-read kernel on the matrix cores for the strip layout NPS_FMT_GT2X (nps_mx.hip) -----------------
-// cohort = [strip of 2048 samples][superblock of 128 rows][unit of 32 samples][row][8 bytes]; codes 0, 1, 2 =
-// dosage, 3 = missing; sample s of a unit in bits 2s, 2s+1 of the row's 8 bytes.  Every strip but the last has
-// 64 units; the last has what is left.
-struct MxGeom {
-    uint64_t n_units = 0, n_sb = 0;
-    uint32_t P = 0, nu_last = 0;
-};
-static inline MxGeom mx_geom(uint64_t n_samples, uint64_t n_rows) {
-    MxGeom g;
-    g.n_units = (n_samples + 31) / 32;
-    g.n_sb = (n_rows + 127) / 128;
-    g.P = (uint32_t)((g.n_units + 63) / 64);
-    g.nu_last = g.P ? (uint32_t)(g.n_units - 64ull * (g.P - 1)) : 0u;
-    return g;
-}
+// layout, geometry (MxGeom), plan (MxPlan) and route (mx_route): nps_mx_route.h, free of HIP
 static inline uint64_t gt2x_superblocks(uint64_t n_rows) { return (n_rows + 127) / 128; }
 static inline uint64_t gt2x_bytes(uint64_t n_samples, uint64_t n_rows) {
     const MxGeom g = mx_geom(n_samples, n_rows);
@@ -292,49 +279,51 @@ static __host__ __device__ inline uint64_t gt2x_unit_index(uint64_t unit, uint64
     const uint64_t nu = p == P - 1 ? n_units - 64 * (P - 1) : 64;
     return p * 64 * n_sb + sb * nu + (unit & 63);
 }
-struct MxPlan {
-    bool ok = false;
-    bool given = false;  // the shape does not fit one cooperative grid (more strips than compute units): the row
-                         // tallies come from launch_mx_tally, the accumulation runs as an ordinary grid (two reads)
-    uint32_t P = 0, Q = 0, nu_last = 0, n_sb = 0, n_flush = 0;  // strips, row teams per strip (superblock k belongs to team k % Q)
-    uint64_t cpart_floats = 0;  // digit sums handed to mx_fold_kernel
-    // the first form (launch_fused_mx) may cut the unit sequence into strips of U = 62 units instead of the layout's 64
-    // where that puts more compute units to work (500 000 samples: 253 strips instead of 245): Pv strips, the last of
-    // nu_last_v units.  U = 64: Pv = P.  Every other kernel works on the layout's strips.
-    uint32_t U = 64, Pv = 0, nu_last_v = 0;
-};
-// two_pass: plan the tally + accumulate pair whatever the shape (NPS_MODE_TWOPASS)
+static_assert(kMxModeAuto == NPS_MODE_AUTO && kMxModeTwoPass == NPS_MODE_TWOPASS && kMxModeFused == NPS_MODE_FUSED, "nps_mx_route.h");
+// mx_plan_for with the device's compute units (looked up once per device)
+hipError_t mx_cus(int device, int *cus);
 hipError_t mx_plan(int device, uint64_t n_samples, uint64_t n_rows, bool two_pass, MxPlan *plan);
-// d_tally: [n_sb*128] zeroed; d_tally1: [ceil(P/16)][n_sb*128] zeroed (both are zero again after launch_mx_fold); d_cpart: [plan.cpart_floats]; d_const_sum: 2 * plan.Q doubles, zero on entry (the caller zeroes them again after launch_mx_fold); d_pre: 32 bytes
-// per row (scratch, written by the pass's first launch);
-// t_maxmis: largest nmissing with !((double)nmissing / (double)N > --maxmis); F: fixed-point scale 2^F with
-// |beta| (4 + max(2, 2 |eaf|)) 2^F < 2^56 for every row
-hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, uint64_t n_rows, const nps_row_desc *d_desc, DevParams prm,
-                           int64_t t_maxmis, int F, void *d_pre, unsigned long long *d_tally,
-                           unsigned long long *d_tally1, nps_locus_stat *d_stats,
-                           unsigned long long *d_nloci, double *d_const_sum, float *d_cpart, unsigned int *d_timeout);
+// One band of a run, as the engine hands it to launch_fused_mx / launch_mx_given and then to launch_mx_fold.
+struct MxRun {
+    const void *d_units = nullptr;  // the cohort, of n_sb_cohort superblocks; the run starts at superblock sb0
+    uint64_t n_sb_cohort = 0, sb0 = 0, n_samples = 0, n_rows = 0;
+    const nps_row_desc *d_desc = nullptr;
+    DevParams prm{};
+    int64_t t_maxmis = -1;  // largest nmissing with !((double)nmissing / (double)N > --maxmis)
+    int F = 0;              // fixed-point scale 2^F with |beta| (4 + max(2, 2 |eaf|)) 2^F < 2^56 for every row
+    unsigned long long *d_tally = nullptr;  // [plan.n_sb * 128], zero on entry and again after launch_mx_fold
+    nps_locus_stat *d_stats = nullptr;
+    unsigned long long *d_nloci = nullptr;
+    double *d_const_sum = nullptr;      // 2 * plan.Q doubles, zero on entry (the caller zeroes them again after launch_mx_fold)
+    float *d_cpart = nullptr;           // [plan.cpart_floats]
+    unsigned int *d_timeout = nullptr;  // raised by a bounded wait that expired (launch_mx_given: for the operand tables)
+    // launch_fused_mx only
+    void *d_pre = nullptr;                   // 32 bytes per row (scratch, written by the pass's first launch)
+    unsigned long long *d_tally1 = nullptr;  // [ceil(P/16)][plan.n_sb * 128], zero on entry and again after launch_mx_fold
+    // launch_mx_given only
+    const unsigned long long *d_tally_given = nullptr;  // the complete tallies: kept with the cohort, or d_tally after launch_mx_tally
+    void *d_ops = nullptr;                              // 48 bytes per row padded to 128 rows
+    double *d_const_part = nullptr;                     // one double per superblock
+    unsigned int *d_done = nullptr;                     // one zeroed word (zero again afterwards)
+    // launch_mx_fold only: part0[i] (+)= the band's sums (overwrite != 0: written, not read); a raised timeout word is ORed
+    // into *d_status; d_keep (or nullptr): the run's complete tally words (nmissing << 28 | neffect, arrival count stripped)
+    // are copied there before they are zeroed -- the cohort's kept tallies as a by-product of a single-read pass
+    double *d_part0 = nullptr;
+    int overwrite = 0;
+    unsigned long long *d_status = nullptr, *d_keep = nullptr;
+    uint64_t n_keep = 0;
+};
+// the single-read kernel (plan without `given`): the tallies are counted in the pass
+hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const MxRun &r);
 // plan.given only: the whole-row tallies of the run's rows into d_tally (zero on entry), one read of the matrix
 hipError_t launch_mx_tally(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
                            uint64_t n_samples, unsigned long long *d_tally);
-// keep (or nullptr): the run's complete tally words (nmissing << 28 | neffect, arrival count stripped) are copied there
-// before they are zeroed -- the cohort's kept tallies as a by-product of a single-read pass
-hipError_t launch_mx_fold(hipStream_t st, const MxPlan &plan, const float *d_cpart, uint64_t n_samples, int F,
-                          const double *d_const_sum, double *d_part0, int overwrite, unsigned long long *d_tally,
-                          uint64_t n_tally, unsigned long long *d_tally1, uint64_t n_tally1, unsigned int *d_timeout,
-                          unsigned long long *d_status,
-                          bool vstrips = false /* the digit sums come from launch_fused_mx with plan.U < 64 */,
-                          unsigned long long *d_keep = nullptr, uint64_t n_keep = 0);
+// nps_mxg.hip: the run with its row tallies GIVEN (plan.given): per-row decisions + operands, then an ordinary grid of
+// P x Q workgroups
+hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const MxRun &r);
+// epilogue of either kernel: the digit sums of the plan's grid into part0, the tally words zeroed
+hipError_t launch_mx_fold(hipStream_t st, const MxPlan &plan, const MxRun &r);
 hipError_t launch_mx_prep(hipStream_t st, const nps_row_desc *d_desc, uint64_t n_rows, DevParams prm, int F, void *d_pre);
-// nps_mxg.hip: the run with its row tallies GIVEN (plan.given: kept with the cohort, or from launch_mx_tally): per-row
-// decisions + operands, then an ordinary grid of P x Q workgroups.  d_ops: 48 bytes per row padded to 128 rows;
-// d_const_part: one double per superblock; d_done: one zeroed word (zero again afterwards); d_const_sum as for launch_fused_mx
-hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, uint64_t n_rows, const nps_row_desc *d_desc, DevParams prm,
-                           int64_t t_maxmis, int F, const unsigned long long *d_tally, nps_locus_stat *d_stats,
-                           unsigned long long *d_nloci, double *d_const_sum, float *d_cpart, void *d_ops,
-                           double *d_const_part, unsigned int *d_done,
-                           unsigned int *d_timeout /* raised when a wave's wait for its operand tables expires */);
 // rows [row0, row0+n_rows) (row0 a multiple of 128) of a cohort of n_rows_cohort rows; rows past the end inside
 // the last superblock written become zero
 hipError_t launch_synth_gt2x(hipStream_t st, void *d_units, uint64_t n_samples, uint64_t n_rows_cohort, uint64_t row0,

@@ -861,67 +861,29 @@ hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint
     return hipGetLastError();
 }
 
+hipError_t mx_cus(int device, int *cus) {
+    static int cus_cached[64] = {0};
+    *cus = device >= 0 && device < 64 ? cus_cached[device] : 0;
+    if (*cus) return hipSuccess;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return e;
+    *cus = prop.multiProcessorCount;
+    if (device >= 0 && device < 64) cus_cached[device] = *cus;
+    return hipSuccess;
+}
+
 hipError_t mx_plan(int device, uint64_t n_samples, uint64_t n_rows, bool two_pass, MxPlan *plan) {
     *plan = MxPlan{};
-    if (n_samples == 0 || n_rows == 0 || n_samples >= (1ull << 27)) return hipSuccess;
-    static int cus_cached[64] = {0};
-    int cus = device >= 0 && device < 64 ? cus_cached[device] : 0;
-    if (!cus) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, device);
-        if (e != hipSuccess) return e;
-        cus = prop.multiProcessorCount;
-        if (device >= 0 && device < 64) cus_cached[device] = cus;
-    }
-    const MxGeom gm = mx_geom(n_samples, n_rows);
-    if (gm.n_sb > 0x1fffffffull || gm.P > 65535u) return hipSuccess;
-    plan->P = gm.P;
-    plan->nu_last = gm.nu_last;
-    plan->n_sb = (uint32_t)gm.n_sb;
-    // One strip per compute unit, the whole grid resident (8-bit arrival count): the single-read kernel.  Fewer strips
-    // than compute units: Q row teams per strip fill the chip (superblock k belongs to team k % Q).  More strips than
-    // compute units (N > 2048 x CUs): the tallies come from their own pass and the accumulation runs as an ordinary
-    // grid of P x Q independent workgroups, about four per compute unit for an even tail.
-    plan->given = two_pass || gm.P > (uint32_t)cus || gm.P > 255;
-    uint64_t q = (uint64_t)cus / gm.P;
-    if (plan->given) {
-        // independent workgroups, one resident per compute unit at a time: P x Q of them run in ceil(P Q / CUs) rounds.
-        // Of the team counts that give between two and eight rounds, the one whose last round is fullest (147 strips:
-        // Q = 7 would be 1029 workgroups = four rounds and five stragglers; Q = 12 is 1764 = seven rounds, 98 % full)
-        const uint64_t lo = std::max<uint64_t>(1, ((uint64_t)2 * cus + gm.P - 1) / gm.P), hi = std::max<uint64_t>(lo, (uint64_t)8 * cus / gm.P);
-        double best = -1.0;
-        q = lo;
-        for (uint64_t t = lo; t <= hi; ++t) {
-            const uint64_t wg = (uint64_t)gm.P * t, rounds = (wg + cus - 1) / cus;
-            const double fill = (double)wg / (double)(rounds * cus);
-            if (fill > best + 1e-9) {
-                best = fill;
-                q = t;
-            }
-        }
+    if (n_samples == 0 || n_rows == 0 || n_samples >= (1ull << 27)) return hipSuccess;  // (no device is asked for these)
+    int cus = 0;
+    hipError_t e = mx_cus(device, &cus);
+    if (e != hipSuccess) return e;
+    uint64_t force_q = 0;
 #ifdef NPS_DIAGNOSTICS
-        if (getenv("NPS_MXG_Q")) q = (uint64_t)std::max(1, atoi(getenv("NPS_MXG_Q")));
+    if (getenv("NPS_MXG_Q")) force_q = (uint64_t)std::max(1, atoi(getenv("NPS_MXG_Q")));
 #endif
-    }
-    q = std::max<uint64_t>(1, std::min<uint64_t>(q, gm.n_sb));
-    plan->Q = (uint32_t)q;
-    const uint64_t n_t = (gm.n_sb + q - 1) / q;  // superblocks of the longest team
-    plan->n_flush = (uint32_t)((n_t + kFlushSb - 1) / kFlushSb);
-    // virtual strips of 62 units for the first form: only where one row team per strip is all there is (more than half the
-    // compute units are strips already) and the finer cut still fits the resident grid
-    plan->U = 64;
-    plan->Pv = gm.P;
-    plan->nu_last_v = gm.nu_last;
-    if (!plan->given && q == 1) {
-        const uint64_t total_units = (uint64_t)(gm.P - 1) * 64 + gm.nu_last, pv = (total_units + 61) / 62;
-        if (pv > gm.P && pv <= (uint64_t)cus && pv <= 255) {
-            plan->U = 62;
-            plan->Pv = (uint32_t)pv;
-            plan->nu_last_v = (uint32_t)(total_units - (pv - 1) * 62);
-        }
-    }
-    plan->cpart_floats = (uint64_t)plan->n_flush * q * std::max(gm.P, plan->Pv) * 64 * 2 * 256;
-    plan->ok = true;
+    *plan = mx_plan_for(cus, n_samples, n_rows, two_pass, force_q);
     return hipSuccess;
 }
 
@@ -951,21 +913,17 @@ hipError_t launch_mx_prep(hipStream_t st, const nps_row_desc *d_desc, uint64_t n
 #endif
 constexpr uint32_t kMxFewStrips = NPS_MX_FEW_STRIPS;  // layout strips up to which the 9|10|8|4 split is used (one row team)
 
-hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, uint64_t n_rows, const nps_row_desc *d_desc, DevParams prm,
-                           int64_t t_maxmis, int F, void *d_pre, unsigned long long *d_tally,
-                           unsigned long long *d_tally1, nps_locus_stat *d_stats,
-                           unsigned long long *d_nloci, double *d_const_sum, float *d_cpart, unsigned int *d_timeout) {
+hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const MxRun &r) {
     {
-        hipError_t pe = launch_mx_prep(st, d_desc, n_rows, prm, F, d_pre);
+        hipError_t pe = launch_mx_prep(st, r.d_desc, r.n_rows, r.prm, r.F, r.d_pre);
         if (pe != hipSuccess) return pe;
     }
     // one row team (more than 128 strips): the control waves carry two units instead of five (see fused_mx_kernel)
     if (plan.given) return hipErrorInvalidValue;  // (given tallies: launch_mx_given, nps_mxg.hip)
-    const bool light_ctl = plan.Q == 1, vstrips = light_ctl && plan.U < 64;
+    const bool light_ctl = plan.Q == 1, vstrips = plan.grid_U != 64;
     const void *fn = nullptr;
     if (vstrips) {
-        switch (plan.U) {
+        switch (plan.grid_U) {
         // 10|10|9|2 where the strips fill the chip; with fewer strips (up to ~176 of the layout's: 360 000 samples) the step is
         // the two data waves of SIMD 0 / 1 (nineteen units x ~300 cycles) while the control waves wait 1 600 cycles at the
         // barrier (profiles/r06_mx_timers.txt, 300 000 samples): 9|10|8|4 moves two units per SIMD pair over to them
@@ -983,7 +941,7 @@ hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_uni
     // diagnostics builds only (tools/mkexp.sh -DNPS_DIAGNOSTICS): NPS_MX_DEBUG selects a kernel with parts left out (1 no tally
     // popcounts, 4 no hand-over, 5 neither), NPS_MX_SPLIT=UA,U2,UB,UC another split of a 62-unit strip over the eight waves
     static const int dbg = getenv("NPS_MX_DEBUG") ? atoi(getenv("NPS_MX_DEBUG")) : 0;
-    if (vstrips && plan.U == 62) {
+    if (plan.grid_U == 62) {
         switch (dbg) {
         case 1: fn = (const void *)fused_mx_kernel<1, false, 10, 10, 9, 2, true, 62>; break;
         case 4: fn = (const void *)fused_mx_kernel<4, false, 10, 10, 9, 2, true, 62>; break;
@@ -1019,30 +977,30 @@ hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_uni
         }
     }
     MxArgs a;
-    a.units = (const v4u *)d_units;
-    a.n_sb_cohort = n_sb_cohort;
-    a.sb0 = (uint32_t)sb0;
+    a.units = (const v4u *)r.d_units;
+    a.n_sb_cohort = r.n_sb_cohort;
+    a.sb0 = (uint32_t)r.sb0;
     a.n_sb = plan.n_sb;
-    a.n_rows = n_rows;
-    a.n_samples = n_samples;
-    a.P = vstrips ? plan.Pv : plan.P;
-    a.nu_last = vstrips ? plan.nu_last_v : plan.nu_last;
-    a.U = vstrips ? plan.U : 64u;
+    a.n_rows = r.n_rows;
+    a.n_samples = r.n_samples;
+    a.P = plan.grid_P;
+    a.nu_last = plan.grid_nu_last;
+    a.U = plan.grid_U;
     a.P_phys = plan.P;
     a.nu_last_phys = plan.nu_last;
     a.Q = plan.Q;
-    a.desc = d_desc;
-    a.pre = (const MxPre *)d_pre;
-    a.prm = prm;
-    a.t_maxmis = t_maxmis;
-    a.scale = std::ldexp(1.0, F);
-    a.tally = d_tally;
-    a.tally1 = d_tally1;
-    a.stats = d_stats;
-    a.nloci = d_nloci;
-    a.const_sum = d_const_sum;
-    a.cpart = d_cpart;
-    a.timeout = d_timeout;
+    a.desc = r.d_desc;
+    a.pre = (const MxPre *)r.d_pre;
+    a.prm = r.prm;
+    a.t_maxmis = r.t_maxmis;
+    a.scale = std::ldexp(1.0, r.F);
+    a.tally = r.d_tally;
+    a.tally1 = r.d_tally1;
+    a.stats = r.d_stats;
+    a.nloci = r.d_nloci;
+    a.const_sum = r.d_const_sum;
+    a.cpart = r.d_cpart;
+    a.timeout = r.d_timeout;
     a.ctl_prio = plan.P <= 208 ? 1u : 0u;
     // strips per first-stage group (measured at 16 / 32 / 48 / 64, ms per 1M rows: 200 000 samples 9.48 / 9.27 / 9.07 /
     // 9.09, 400 000 20.1 / 19.6 / 19.6 / 19.7, 500 000 23.80 / 23.55 / 23.48 / 23.49; 8: slower, 128: slower)
@@ -1055,7 +1013,7 @@ hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_uni
     }
     if (getenv("NPS_MX_PRIO")) a.ctl_prio = (uint32_t)atoi(getenv("NPS_MX_PRIO"));
 #endif
-    const dim3 grid((vstrips ? plan.Pv : plan.P) * plan.Q);
+    const dim3 grid(plan.grid_P * plan.Q);
     void *args[] = {&a};
 #ifdef NPS_MX_TIMERS
     {
@@ -1079,17 +1037,14 @@ hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const void *d_uni
     return hipLaunchCooperativeKernel(fn, grid, dim3(kMxThreads), args, kLdsBytes, st);
 }
 
-hipError_t launch_mx_fold(hipStream_t st, const MxPlan &plan, const float *d_cpart, uint64_t n_samples, int F,
-                          const double *d_const_sum, double *d_part0, int overwrite, unsigned long long *d_tally,
-                          uint64_t n_tally, unsigned long long *d_tally1, uint64_t n_tally1, unsigned int *d_timeout,
-                          unsigned long long *d_status, bool vstrips, unsigned long long *d_keep, uint64_t n_keep) {
+hipError_t launch_mx_fold(hipStream_t st, const MxPlan &plan, const MxRun &r) {
     (void)hipGetLastError();
-    if (n_keep > n_tally) return hipErrorInvalidValue;
-    const uint64_t blocks = std::max<uint64_t>(std::max<uint64_t>(1, (n_samples + 255) / 256), std::min<uint64_t>(4096, n_tally1 / 1024));
-    hipLaunchKernelGGL(mx_fold_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, d_cpart, plan.n_sb, plan.Q,
-                       vstrips ? plan.Pv : plan.P, vstrips ? plan.U : 64u, n_samples,
-                       std::ldexp(1.0, -F), d_const_sum, d_part0, overwrite, d_tally, n_tally, d_tally1, n_tally1, d_timeout,
-                       d_status, d_keep, n_keep);
+    const uint64_t n_tally = (uint64_t)plan.n_sb * 128, n_tally1 = (uint64_t)((plan.P + 15) / 16) * n_tally;
+    if (r.n_keep > n_tally) return hipErrorInvalidValue;
+    const uint64_t blocks = std::max<uint64_t>(std::max<uint64_t>(1, (r.n_samples + 255) / 256), std::min<uint64_t>(4096, n_tally1 / 1024));
+    hipLaunchKernelGGL(mx_fold_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, r.d_cpart, plan.n_sb, plan.Q, plan.grid_P,
+                       plan.grid_U, r.n_samples, std::ldexp(1.0, -r.F), r.d_const_sum, r.d_part0, r.overwrite, r.d_tally, n_tally,
+                       r.d_tally1, n_tally1, r.d_timeout, r.d_status, r.d_keep, r.n_keep);
     return hipGetLastError();
 }
 

@@ -36,7 +36,7 @@ constexpr int kMxThreads = (kDW + 2) * 64;
 constexpr int kUD = NPS_MX_UD;
 constexpr int kUC = NPS_MX_UC;           // units of the two control waves, which do the per-row work of 64 rows each
 constexpr int kTabBufs = 2;
-constexpr uint32_t kFlushSb = 1024;      // superblocks between flushes of the float32 digit sums (131 072 rows x 75 < 2^24)
+// (kFlushSb, superblocks between flushes of the float32 digit sums: nps_mx_route.h, which sizes them)
 constexpr uint32_t kLdsTables = 131072;  // [kTabBufs][3 operands][128 rows][16 bytes]
 constexpr uint32_t kLdsTally = kLdsTables + kTabBufs * 6144;  // [2][128] uint32: nmissing << 16 | neffect of the strip
 constexpr uint32_t kLdsBytes = kLdsTally + 1024;

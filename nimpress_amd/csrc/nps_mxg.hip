@@ -318,39 +318,25 @@ __global__ __launch_bounds__(kGW * 64, kGW / 4) void mx_given_kernel(const MxgAr
 
 // d_ops: 48 bytes per row of the run padded to 128; d_const_part: one double per superblock; d_done: one zeroed word;
 // d_const_sum[0] receives the locus constants (the other 2 Q - 1 slots stay zero), as mx_fold_kernel expects them
-hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, uint64_t n_rows, const nps_row_desc *d_desc, DevParams prm,
-                           int64_t t_maxmis, int F, const unsigned long long *d_tally, nps_locus_stat *d_stats,
-                           unsigned long long *d_nloci, double *d_const_sum, float *d_cpart, void *d_ops,
-                           double *d_const_part, unsigned int *d_done, unsigned int *d_timeout) {
+hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const MxRun &r) {
     if (!plan.ok || !plan.given) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    MxArgs ra;  // (what mx_row reads)
-    ra.units = nullptr;
-    ra.n_sb_cohort = 0;
-    ra.sb0 = 0;
+    MxArgs ra{};  // (what mx_row reads; everything else null / zero)
     ra.n_sb = plan.n_sb;
-    ra.n_rows = n_rows;
-    ra.n_samples = n_samples;
+    ra.n_rows = r.n_rows;
+    ra.n_samples = r.n_samples;
     ra.P = plan.P;
     ra.nu_last = plan.nu_last;
     ra.Q = plan.Q;
-    ra.desc = d_desc;
-    ra.pre = nullptr;
-    ra.prm = prm;
-    ra.t_maxmis = t_maxmis;
-    ra.scale = std::ldexp(1.0, F);
-    ra.tally = nullptr;
-    ra.tally1 = nullptr;
-    ra.stats = d_stats;
-    ra.nloci = d_nloci;
-    ra.const_sum = d_const_sum;
-    ra.cpart = nullptr;
-    ra.timeout = nullptr;
-    ra.ctl_prio = 0;
-    ra.grp_strips = 0;
-    hipLaunchKernelGGL(mx_ops_kernel, dim3(plan.n_sb), dim3(128), 0, st, d_desc, n_rows, d_tally, ra, (v4u *)d_ops,
-                       d_const_part, d_done);
+    ra.desc = r.d_desc;
+    ra.prm = r.prm;
+    ra.t_maxmis = r.t_maxmis;
+    ra.scale = std::ldexp(1.0, r.F);
+    ra.stats = r.d_stats;
+    ra.nloci = r.d_nloci;
+    ra.const_sum = r.d_const_sum;
+    hipLaunchKernelGGL(mx_ops_kernel, dim3(plan.n_sb), dim3(128), 0, st, r.d_desc, r.n_rows, r.d_tally_given, ra, (v4u *)r.d_ops,
+                       r.d_const_part, r.d_done);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     static bool attr_set = false;
@@ -360,16 +346,16 @@ hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const void *d_uni
         attr_set = true;
     }
     MxgArgs a;
-    a.units = (const v4u *)d_units;
-    a.n_sb_cohort = n_sb_cohort;
-    a.sb0 = (uint32_t)sb0;
+    a.units = (const v4u *)r.d_units;
+    a.n_sb_cohort = r.n_sb_cohort;
+    a.sb0 = (uint32_t)r.sb0;
     a.n_sb = plan.n_sb;
     a.P = plan.P;
     a.nu_last = plan.nu_last;
     a.Q = plan.Q;
-    a.ops = (const v4u *)d_ops;
-    a.cpart = d_cpart;
-    a.timeout = d_timeout;
+    a.ops = (const v4u *)r.d_ops;
+    a.cpart = r.d_cpart;
+    a.timeout = r.d_timeout;
     hipLaunchKernelGGL(mx_given_kernel, dim3(plan.P * plan.Q), dim3(kGW * 64), kGLdsBytes, st, a);
 #ifdef NPS_MX_TIMERS
     {

@@ -21,7 +21,7 @@ U = 2.0 ** -53                     # unit roundoff of float64
 LOCUS = {"ps": 0, "homref": 1, "fail": 2, "ignore": 3}
 SAMPLE_INTERNAL = ("int_ps", "int_fail")
 CODE_DOSAGE = np.array([0.0, 1.0, np.nan, 2.0])   # 2-bit codes (tests/special_cases.py): 2 = missing
-FLUSH_SB = 1024                    # kFlushSb, nps_mx_common.h:39
+FLUSH_SB = 1024                    # kFlushSb, nps_mx_route.h
 BAND_BITS, MAX_BANDS = 30, 8       # kMxBandBits, kMxMaxBands, nps_engine.hip:1469
 
 
@@ -516,7 +516,8 @@ def column_peak(block, beta, samples, flush_sb=FLUSH_SB, Q=1):
 
 
 def given_teams(n_strips, cus, n_sb):
-    """row teams of the given-tallies plan (mx_plan with two_pass, nps_mx.hip:836-857): of the team counts that give 2 to
+    """row teams of the given-tallies plan (mx_plan_for with two_pass, nps_mx_route.h;
+    tests/test_mx_route.py holds the two together): of the team counts that give 2 to
     8 rounds of the grid, the one whose last round is fullest"""
     lo = max(1, (2 * cus + n_strips - 1) // n_strips)
     hi = max(lo, 8 * cus // n_strips)

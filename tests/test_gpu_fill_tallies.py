@@ -293,3 +293,26 @@ def test_two_threads_score_one_uploaded_cohort():
             assert nloci == ref_nloci
             assert np.array_equal(scores.view(np.int64), ref_scores.view(np.int64))
     dev.close()
+
+
+@pytest.mark.parametrize("n,geometry", [(253_952, (124, 2, 2048)), (264_192, (134, 1, 1984))])
+def test_fused_geometry_reports_the_grid_the_pass_ran_on(n, geometry):
+    """on both sides of the switch to strips of 62 units (124 strips, two row teams: the layout's strips of 2048 samples;
+    129 strips, one team: 134 strips of 62 units = 1984 samples) nps_fused_geometry tells the grid of the single-read
+    kernel, and that kernel and its fold agree on it: a device-generated cohort scored once under NPS_MODE_FUSED gives the
+    oracle's statistics and scores on the same rows"""
+    m = 256
+    co = make_cohort(n, m, 606 + n, np.random.default_rng(n))
+    kw = PARAM_GRID[0]
+    dev = capi.Cohort(n, m, fmt=capi.FMT_GT2X)
+    dev.synth(0, co["seed"], co["th"], co["tm"], co["tmi"])
+    sc = capi.Scorer(n, capi.make_params(**kw))
+    assert sc.fused_geometry(m, capi.FMT_GT2X) == geometry
+    sc.close()
+    p, stats, scores, nloci = run_pass(dev, n, kw, capi.row_descs(co["beta"], co["eaf"], None, co["rie"]), mode=capi.MODE_FUSED)
+    assert in_pass(p) and p.n_tally == 0
+    ref_scores, ref_stats, ref_nloci = oracle_scores(co, kw, 0.0)
+    assert nloci == ref_nloci
+    assert_stats_equal(stats, [tuple(s) for s in ref_stats])
+    check_scores(scores, ref_scores, co["beta"], nloci)
+    dev.close()

@@ -158,6 +158,9 @@ def partial_sharded(D, d, key):
         nl += sc.partial_device(part.data_ptr())
         total = part if total is None else total + part
         scs.append(sc)
+    # the sum of the shards is torch's work on torch's stream; a context's stream does not wait for it
+    # (hipStreamNonBlocking): without this the normalisation can run first and the sum then overwrites it
+    torch.cuda.synchronize()
     scs[0].normalize_device(total.data_ptr(), nl, d["offset"])
     torch.cuda.synchronize()
     out = total.cpu().numpy()
