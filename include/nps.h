@@ -475,6 +475,10 @@ void *nps_stream(nps_ctx *ctx);
  * layout's strips) */
 int nps_fused_geometry(nps_ctx *ctx, int format, uint64_t n_rows, uint32_t *slices, uint32_t *teams,
                        uint32_t *samples_per_slice);
+/* The number of HIP resources (device allocations, pinned host allocations, events, streams) that the objects of this
+ * library hold in this process right now: 0 while none of them is alive, also where there is no device.  A destroyed
+ * object gives back everything it took; a refused or failed call leaves the number as it found it.  For leak tests. */
+int64_t nps_live_resources(void);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,7 @@ SYMBOLS = [
     "nps_cohort_convert", "nps_cohort_row_tallies", "nps_cohort_keep_tallies", "nps_cohort_has_tallies", "nps_multi_set_missing_weight_bits",
     "nps_cohort_push_gt_raw", "nps_cohort_push_bed", "nps_multi_partial_device", "nps_multi_partial",
     "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes", "nps_cohort_rows_tallied",
+    "nps_live_resources",
 ]
 
 
@@ -205,6 +206,10 @@ def load(with_torch: bool = True):
     L.nps_cohort_expect_passes.argtypes = [vp, C.c_uint32]
     L.nps_cohort_has_tallies.argtypes = [vp]
     L.nps_cohort_rows_tallied.argtypes = [vp, u64, u64]
+    L.nps_cohort_push_gt_raw.argtypes = [vp, u64, vp, i32, i32, i32]
+    L.nps_cohort_push_bed.argtypes = [vp, u64, vp, i32]
+    L.nps_live_resources.argtypes = []
+    L.nps_live_resources.restype = C.c_int64
     _lib = L
     return L
 
@@ -223,6 +228,11 @@ def make_params(imp_locus="ps", imp_missing="homref", imp_sample="int_ps", maxmi
 
 def device_count() -> int:
     return load().nps_device_count()
+
+
+def live_resources() -> int:
+    """HIP resources (allocations, events, streams) the library's objects hold right now (nps_live_resources)"""
+    return int(load().nps_live_resources())
 
 
 class Cohort:
@@ -278,6 +288,19 @@ class Cohort:
         assert th.size == tm.size == tmi.size
         _check(load().nps_cohort_synth_rows(self._h, row0, th.size, gen_row0, seed, th.ctypes.data,
                                             tm.ctypes.data, tmi.ctypes.data))
+
+    def push_gt_raw(self, row: int, gt: np.ndarray, ploidy: int, eaidx: int):
+        """one row of a FMT_GT2 cohort from the typed GT vector of a BCF record (int8 / int16 / int32, n * ploidy values),
+        decoded on the device (nps_cohort_push_gt_raw)"""
+        gt = np.ascontiguousarray(gt)
+        assert gt.dtype in (np.int8, np.int16, np.int32) and gt.size == self.n_samples * ploidy
+        _check(load().nps_cohort_push_gt_raw(self._h, int(row), gt.ctypes.data, gt.dtype.itemsize, ploidy, eaidx))
+
+    def push_bed(self, row: int, bed_row: np.ndarray, effect_is_a1: int):
+        """one row of a FMT_GT2 cohort from ceil(n/4) bytes of a PLINK .bed file (nps_cohort_push_bed)"""
+        bed_row = np.ascontiguousarray(bed_row, dtype=np.uint8)
+        assert bed_row.size == (self.n_samples + 3) // 4
+        _check(load().nps_cohort_push_bed(self._h, int(row), bed_row.ctypes.data, int(effect_is_a1)))
 
     def convert_from(self, src: "Cohort"):
         """fill this FMT_GT2M cohort (and its row tallies) from a FMT_GT2 cohort of the same shape"""

@@ -20,8 +20,11 @@
 #include <vector>
 
 #include "nps_kernels.h"
+#include "nps_own.h"
 
 using namespace nps;
+
+extern "C" int64_t nps_live_resources(void) { return live_resources.load(); }
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -49,25 +52,28 @@ static int fail(int code, const char *fmt, ...) {
 enum ProfClass { P_DECODE = 0, P_TALLY, P_PARAMS, P_ACCUM, P_FUSED, P_REDUCE, P_COUNT };
 
 struct ProfSpan {
-    hipEvent_t a, b;
+    Event a, b;
     int cls;
 };
 
 struct nps_cohort {
+    // nps_cohort_push_*: rows decoded on the device straight into the cohort (a pinned ring the decode kernel reads
+    // over PCIe, on a stream of the cohort's own); every call that reads the cohort waits for it (cohort_quiesce)
+    Stream push_stream;  // (first: destroyed last)
     int device = 0;
     int format = NPS_FMT_GT2;
     uint64_t n_samples = 0, n_rows = 0;
     uint64_t stride_bytes = 0;  // per row (GT2: rows are interleaved in groups of 4, a group is 4*stride_bytes)
-    void *d_data = nullptr;
+    DevBuf<unsigned char> d_data;
     // nps_cohort_optimize (GT2): the rows are in the parity layout (nps_kernels.h: the high-bit plane of
     // slot 0 of every group holds the XOR of the four rows' planes)
     bool optimized = false;
     // NPS_FMT_GT2M: whole-row tallies (nmissing << 32 | neffect) produced by whatever packed the rows
-    unsigned long long *d_row_tally = nullptr;
+    DevBuf<unsigned long long> d_row_tally;
     // NPS_FMT_GT2X: the whole-row tallies (nmissing << 28 | neffect, the tally word of the strip kernel without its arrival
     // count), one per row of every superblock, allocated (zeroed) on first need.  Counted where the rows are written
     // (upload, upload_bed, convert: the fill kernels), by nps_cohort_keep_tallies, or kept from a scoring pass.
-    unsigned long long *d_mx_row_tally = nullptr;
+    DevBuf<unsigned long long> d_mx_row_tally;
     // Which superblocks' words are complete: one bit per superblock (mx_sb_valid) and the number of bits set.  Contexts on
     // several threads may score one cohort: every WRITER of d_mx_row_tally, of the bitmap and of mx_tally_asked holds
     // tally_mutex and sets a bit (release) only AFTER the superblock's words are in device memory; readers load with
@@ -79,18 +85,19 @@ struct nps_cohort {
     std::atomic<bool> mx_tally_asked{false};
     std::mutex tally_mutex;  // NPS_MODE_AUTO may count them lazily from whichever context scores the cohort first
     std::atomic<uint32_t> expect_passes{0};  // nps_cohort_expect_passes: how often the caller will score this cohort (0: not said)
-    // nps_cohort_push_*: rows decoded on the device straight into the cohort (a pinned ring the decode kernel reads
-    // over PCIe, on a stream of the cohort's own); every call that reads the cohort waits for it (cohort_quiesce)
-    hipStream_t push_stream = nullptr;
-    void *h_push[2] = {nullptr, nullptr};
-    hipEvent_t ev_push[2] = {nullptr, nullptr};
-    size_t push_cap = 0;
+    PinnedBuf h_push[2];  // the ring of nps_cohort_push_* (grown together; [1] is allocated last: its size is the ring's)
+    Event ev_push[2];     // ([1] is created last, after d_push_tally: it stands for "the push state is complete")
     int push_next = 0;
-    unsigned long long *d_push_tally = nullptr;  // scratch word for the decode kernel's tally (a GT2 cohort keeps none)
+    DevBuf<unsigned long long> d_push_tally;  // scratch word for the decode kernel's tally (a GT2 cohort keeps none)
     // NPS_FMT_DS32: rows that hold a value outside [0, 2] (checked when rows are uploaded; the generator clips): while
     // there is one, the cohort is scored by the two-pass kernels (the single-read kernel's fixed-point tallies need the range)
     std::vector<unsigned char> ds_row_bad;
     uint64_t ds_bad_rows = 0;
+
+    ~nps_cohort() {  // nothing on the device may still read or write what the members release
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
 };
 
 // ---- NPS_FMT_GT2X: which superblocks carry their tally words ------------------------------------------------------
@@ -116,14 +123,11 @@ static void mx_tallies_mark(nps_cohort *c, uint64_t sb0, uint64_t n_sb, bool val
 }
 // tally_mutex held, the cohort's device current
 static hipError_t mx_tallies_alloc(nps_cohort *c) {
-    if (c->d_mx_row_tally) return hipSuccess;
-    const size_t bytes = sizeof(unsigned long long) * std::max<uint64_t>(gt2x_superblocks(c->n_rows) * 128, 1);
-    hipError_t e = hipMalloc(&c->d_mx_row_tally, bytes);
-    if (e == hipSuccess) e = hipMemset(c->d_mx_row_tally, 0, bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_mx_row_tally);
-        c->d_mx_row_tally = nullptr;
-    }
+    if (c->d_mx_row_tally.get()) return hipSuccess;
+    const uint64_t words = std::max<uint64_t>(gt2x_superblocks(c->n_rows) * 128, 1);
+    hipError_t e = c->d_mx_row_tally.alloc(words);
+    if (e == hipSuccess) e = hipMemset(c->d_mx_row_tally.get(), 0, sizeof(unsigned long long) * words);
+    if (e != hipSuccess) c->d_mx_row_tally.reset();
     return e;
 }
 // a call that rewrites rows [row0, row0 + nrows) of a strip cohort: their superblocks carry nothing until the writer says so
@@ -137,7 +141,7 @@ static void mx_tallies_rewrite(nps_cohort *c, uint64_t row0, uint64_t nrows) {
 static int mx_keep_tallies_locked(nps_cohort *c);
 
 static int cohort_quiesce(const nps_cohort *c) {
-    if (c && c->push_stream) HIP_TRY(hipStreamSynchronize(c->push_stream));
+    if (c && c->push_stream.get()) HIP_TRY(hipStreamSynchronize(c->push_stream.get()));
     return NPS_OK;
 }
 
@@ -147,9 +151,13 @@ struct PendingRow {
     nps_locus_stat host;
 };
 
+struct MxOpRow {  // nps_mxg.hip (tallies given): the weight operands of one row
+    unsigned char bytes[48];
+};
+
 struct nps_ctx {
+    Stream stream;  // (first: destroyed last)
     int device = 0;
-    hipStream_t stream = nullptr;
     uint64_t n = 0;         // samples
     uint64_t n_words = 0;   // ceil(n/16)
     uint64_t stride_words = 0;
@@ -157,83 +165,73 @@ struct nps_ctx {
 
     // streaming batch
     uint32_t batch_cap = 0, batch_rows = 0;
-    uint32_t *d_codes = nullptr;            // [batch_cap/4 groups][stride_words][4] (interleaved)
-    unsigned long long *d_tally = nullptr;  // [batch_cap]
-    nps_row_desc *d_desc = nullptr;         // [batch_cap]
+    DevBuf<uint32_t> d_codes;               // [batch_cap/4 groups][stride_words][4] (interleaved)
+    DevBuf<unsigned long long> d_tally;     // [batch_cap]
+    DevBuf<nps_row_desc> d_desc;            // [batch_cap]
     nps_row_desc *h_desc = nullptr;         // pinned [batch_cap]
-    double *d_lut = nullptr;                // [batch_cap][4]
-    nps_locus_stat *d_stats = nullptr;      // [batch_cap]
+    DevBuf<double> d_lut;                   // [batch_cap][4]
+    DevBuf<nps_locus_stat> d_stats;         // [batch_cap]
     nps_locus_stat *h_stats = nullptr;      // pinned [batch_cap]
     static constexpr int kRawSlots = 8;  // rows in flight between the caller's buffer and the device
     int32_t *h_raw[kRawSlots] = {};  // pinned staging ring for caller buffers
-    void *h_arena = nullptr;  // ONE pinned allocation holding h_desc, h_stats and h_raw[]
-    hipEvent_t ev_raw[kRawSlots] = {};
+    PinnedBuf h_arena;  // ONE pinned allocation holding h_result, h_desc, h_stats and h_raw[]
+    Event ev_raw[kRawSlots];
     int raw_next = 0;
 
     // FORMAT/DS streaming batch (allocated on the first nps_push_ds)
     uint32_t ds_cap = 0, ds_rows = 0;
     uint64_t ds_stride_f = 0;
-    float *d_ds = nullptr;               // [ds_cap][ds_stride_f]
-    nps_row_desc *d_ds_desc = nullptr;   // [ds_cap]
-    DsTally *d_ds_tally = nullptr;
-    DsRowP *d_ds_rowp = nullptr;
-    nps_locus_stat *d_ds_stats = nullptr;
-    void *h_ds_arena = nullptr;          // pinned: h_ds_desc, h_ds_stats, staging ring
+    DevBuf<float> d_ds;                  // [ds_cap][ds_stride_f]
+    DevBuf<nps_row_desc> d_ds_desc;      // [ds_cap]
+    DevBuf<DsTally> d_ds_tally;
+    DevBuf<DsRowP> d_ds_rowp;
+    DevBuf<nps_locus_stat> d_ds_stats;
+    PinnedBuf h_ds_arena;                // pinned: h_ds_desc, h_ds_stats, staging ring
     nps_row_desc *h_ds_desc = nullptr;
     nps_locus_stat *h_ds_stats = nullptr;
     float *h_ds_raw[2] = {nullptr, nullptr};
-    hipEvent_t ev_ds_raw[2] = {nullptr, nullptr};
+    Event ev_ds_raw[2];                  // ([1] is what ensure_ds creates last: it stands for "the DS batch is complete")
     int ds_raw_next = 0;
-    // resident DS runs
-    uint64_t res_ds_cap = 0;
-    DsTally *d_rds_tally = nullptr;
-    DsRowP *d_rds_rowp = nullptr;
+    // resident DS runs (grown on demand)
+    DevBuf<DsTally> d_rds_tally;
+    DevBuf<DsRowP> d_rds_rowp;
 
-    // raw GT staging for ploidy > 2: a ring of two pinned host buffers (grown on demand), read by the kernel
-    size_t poly_cap = 0;
-    void *h_poly[2] = {nullptr, nullptr};
-    hipEvent_t ev_poly[2] = {nullptr, nullptr};
+    // raw GT staging for ploidy > 2: a ring of two pinned host buffers (grown together on demand), read by the kernel
+    PinnedBuf h_poly[2];  // ([1] is allocated last: its size is the ring's)
+    Event ev_poly[2];
     int poly_next = 0;
 
     // accumulators
     AccumGeom geom{};         // streaming geometry (groups_per_chunk for a full batch)
     uint32_t n_chunks = 1;
-    double *d_part = nullptr;  // [n_chunks][part_chunk_stride]
+    DevBuf<double> d_part;  // [n_chunks][part_chunk_stride]
     // which chunks of d_part hold data: 0 = none yet (nothing has been zeroed either: the first
     // writer overwrites), 1 = chunk 0 only (fused epilogues), n_chunks = all (two-pass kernels)
     uint32_t chunks_used = 0;
-    double *d_scores = nullptr;
-    unsigned long long *d_nloci = nullptr;   // [0] used rows counted on the device, [1] sticky status bits
+    DevBuf<double> d_scores;
+    DevBuf<unsigned long long> d_nloci;      // [0] used rows counted on the device, [1] sticky status bits
     unsigned long long *h_result = nullptr;  // pinned copy of that block
     bool broken = false;                     // a launch sequence failed half-way: nps_reset first
     double const_sum = 0.0;   // contributions of rows without genotype data (host decided)
     uint64_t host_nloci = 0;
 
     // resident runs (nps_score_cohort*): per-row buffers, grown on demand
-    uint64_t res_cap = 0;
-    unsigned long long *d_rtally = nullptr;
-    double *d_rlut = nullptr;
-    nps_locus_stat *d_rstats = nullptr;
-    double *d_part_fused = nullptr;         // [Q][team stride] partial scores of the fused kernel
-    uint64_t part_fused_cap = 0;            // doubles
-    unsigned int *d_timeout = nullptr;      // bounded-wait flag of the fused kernels (cleared by fold_kernel)
-    float *d_mx_cpart = nullptr;            // NPS_FMT_GT2X runs: digit sums handed from fused_mx_kernel to mx_fold_kernel
-    uint64_t mx_cpart_cap = 0;              // floats
-    double *d_mx_const = nullptr;           // ... and the locus constants of rows over --maxmis: [8 scratch][2 Q slots], zero between passes
-    uint64_t mx_const_cap = 0;
-    unsigned long long *d_mx_tally1 = nullptr;  // first-stage tally words (groups of 16 strips), zero between passes
-    uint64_t mx_tally1_cap = 0;
-    void *d_mx_ops = nullptr;                   // nps_mxg.hip (tallies given): 48 bytes of weight operands per row ...
-    uint64_t mx_ops_cap = 0;                    // (in units of 48 bytes)
-    double *d_mx_cblk = nullptr;                // ... and one partial sum of locus constants per superblock
-    uint64_t mx_cblk_cap = 0;
+    DevBuf<unsigned long long> d_rtally;    // [rows] (a pair per row for the single-read DS kernel)
+    DevBuf<double> d_rlut;                  // [rows][4]
+    DevBuf<nps_locus_stat> d_rstats;        // [rows]
+    DevBuf<double> d_part_fused;            // [Q][team stride] partial scores of the fused kernel
+    DevBuf<unsigned int> d_timeout;         // bounded-wait flag of the fused kernels (cleared by fold_kernel)
+    DevBuf<float> d_mx_cpart;               // NPS_FMT_GT2X runs: digit sums handed from fused_mx_kernel to mx_fold_kernel
+    DevBuf<double> d_mx_const;              // ... and the locus constants of rows over --maxmis: [8 scratch][2 Q slots], zero between passes
+    DevBuf<unsigned long long> d_mx_tally1; // first-stage tally words (groups of 16 strips), zero between passes
+    DevBuf<MxOpRow> d_mx_ops;               // nps_mxg.hip (tallies given): the weight operands of every row ...
+    DevBuf<double> d_mx_cblk;               // ... and one partial sum of locus constants per superblock
     // NPS_FMT_GT2X runs of a definition with special rows (nps_scoredef::special): those rows in the row layout, scored
     // in IEEE double by the two-pass kernels, a batch at a time
-    uint32_t *d_sp_plain = nullptr;             // [batch][n_words] plain rows out of the strip layout
-    uint32_t *d_sp_group = nullptr;             // [batch / 4 groups][stride_words][4] interleaved
-    unsigned long long *d_sp_tally = nullptr;   // [batch]
-    double *d_sp_lut = nullptr;                 // [batch][4]
-    uint64_t sp_plain_cap = 0, sp_group_cap = 0, sp_tally_cap = 0, sp_lut_cap = 0;  // (elements)
+    DevBuf<uint32_t> d_sp_plain;                // [batch][n_words] plain rows out of the strip layout
+    DevBuf<uint32_t> d_sp_group;                // [batch / 4 groups][stride_words][4] interleaved
+    DevBuf<unsigned long long> d_sp_tally;      // [batch]
+    DevBuf<double> d_sp_lut;                    // [batch][4]
     bool rtally_clean = false;              // d_rtally is all zero (allocation, or the last fused epilogue)
     // shape -> persistent-grid plan of the last resident run (occupancy queries are slow)
     bool plan_valid = false;
@@ -254,6 +252,11 @@ struct nps_ctx {
     bool profiling = false;
     std::vector<ProfSpan> spans;
     nps_profile prof{};
+
+    ~nps_ctx() {  // queued work may still use what the members release
+        (void)hipSetDevice(device);
+        if (stream.get()) (void)hipStreamSynchronize(stream.get());
+    }
 };
 
 static DevParams dev_params(const nps_params &p) {
@@ -281,19 +284,15 @@ static int check_params(const nps_params *p) {
 struct ProfScope {
     nps_ctx *c;
     int cls;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     ProfScope(nps_ctx *ctx, int k) : c(ctx), cls(k) {
-        if (c->profiling) {
-            if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess)
-                (void)hipEventRecord(a, c->stream);
-            else
-                a = b = nullptr;
-        }
+        if (c->profiling && a.create(hipEventDefault) == hipSuccess && b.create(hipEventDefault) == hipSuccess)
+            (void)hipEventRecord(a.get(), c->stream.get());
     }
     ~ProfScope() {
-        if (a && b) {
-            (void)hipEventRecord(b, c->stream);
-            c->spans.push_back({a, b, cls});
+        if (b.get()) {
+            (void)hipEventRecord(b.get(), c->stream.get());
+            c->spans.push_back({std::move(a), std::move(b), cls});
         }
     }
 };
@@ -301,16 +300,14 @@ struct ProfScope {
 static void resolve_spans(nps_ctx *c) {
     for (auto &s : c->spans) {
         float ms = 0.f;
-        (void)hipEventSynchronize(s.b);
-        (void)hipEventElapsedTime(&ms, s.a, s.b);
+        (void)hipEventSynchronize(s.b.get());
+        (void)hipEventElapsedTime(&ms, s.a.get(), s.b.get());
         double *acc[P_COUNT] = {&c->prof.ms_decode, &c->prof.ms_tally,  &c->prof.ms_params,
                                 &c->prof.ms_accumulate, &c->prof.ms_fused, &c->prof.ms_reduce};
         uint64_t *cnt[P_COUNT] = {&c->prof.n_decode, &c->prof.n_tally,  &c->prof.n_params,
                                   &c->prof.n_accumulate, &c->prof.n_fused, &c->prof.n_reduce};
         *acc[s.cls] += ms;
         *cnt[s.cls] += 1;
-        (void)hipEventDestroy(s.a);
-        (void)hipEventDestroy(s.b);
     }
     c->spans.clear();
 }
@@ -332,7 +329,7 @@ __global__ void warmup_kernel(unsigned int *p) {
 extern "C" int nps_warmup(int device) {
     int rc = select_device(device);
     if (rc) return rc;
-    HIP_TRY(hipFree(nullptr));  // the primary context
+    HIP_TRY(hipDeviceSynchronize());  // the primary context
     (void)hipGetLastError();
     hipLaunchKernelGGL(warmup_kernel, dim3(1), dim3(1), 0, nullptr, (unsigned int *)nullptr);  // the code object
     HIP_TRY(hipGetLastError());
@@ -363,62 +360,11 @@ static void choose_geometry(nps_ctx *c) {
     c->geom.part_chunk_stride = (uint64_t)tiles * 256 * 16;
 }
 
-static void free_ctx(nps_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto &s : c->spans) {
-        (void)hipEventDestroy(s.a);
-        (void)hipEventDestroy(s.b);
-    }
-    (void)hipFree(c->d_codes);
-    (void)hipFree(c->d_tally);
-    (void)hipFree(c->d_desc);
-    (void)hipHostFree(c->h_arena);
-    (void)hipFree(c->d_lut);
-    (void)hipFree(c->d_stats);
-    for (int k = 0; k < nps_ctx::kRawSlots; ++k)
-        if (c->ev_raw[k]) (void)hipEventDestroy(c->ev_raw[k]);
-    (void)hipFree(c->d_ds);
-    for (int k = 0; k < 2; ++k) {
-        (void)hipHostFree(c->h_poly[k]);
-        if (c->ev_poly[k]) (void)hipEventDestroy(c->ev_poly[k]);
-    }
-    (void)hipFree(c->d_ds_desc);
-    (void)hipFree(c->d_ds_tally);
-    (void)hipFree(c->d_ds_rowp);
-    (void)hipFree(c->d_ds_stats);
-    (void)hipHostFree(c->h_ds_arena);
-    for (int k = 0; k < 2; ++k)
-        if (c->ev_ds_raw[k]) (void)hipEventDestroy(c->ev_ds_raw[k]);
-    (void)hipFree(c->d_rds_tally);
-    (void)hipFree(c->d_rds_rowp);
-    (void)hipFree(c->d_part_fused);
-    (void)hipFree(c->d_timeout);
-    (void)hipFree(c->d_mx_cpart);
-    (void)hipFree(c->d_mx_const);
-    (void)hipFree(c->d_mx_tally1);
-    (void)hipFree(c->d_mx_ops);
-    (void)hipFree(c->d_mx_cblk);
-    (void)hipFree(c->d_sp_plain);
-    (void)hipFree(c->d_sp_group);
-    (void)hipFree(c->d_sp_tally);
-    (void)hipFree(c->d_sp_lut);
-    (void)hipFree(c->d_rtally);
-    (void)hipFree(c->d_rlut);
-    (void)hipFree(c->d_rstats);
-    (void)hipFree(c->d_part);
-    (void)hipFree(c->d_scores);
-    (void)hipFree(c->d_nloci);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
 static int zero_state(nps_ctx *c) {
     // d_part is not touched: chunks_used = 0 makes the first writer overwrite it
-    HIP_TRY(hipMemsetAsync(c->d_nloci, 0, 3 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_nloci.get(), 0, 3 * sizeof(unsigned long long), c->stream.get()));
     if (c->batch_rows)  // tallies of rows decoded into the open batch (the array is zero otherwise)
-        HIP_TRY(hipMemsetAsync(c->d_tally, 0, sizeof(unsigned long long) * c->batch_rows, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->batch_rows, c->stream.get()));
     c->chunks_used = 0;
     c->broken = false;
     c->const_sum = 0.0;
@@ -437,9 +383,9 @@ static int zero_state(nps_ctx *c) {
 // the two-pass kernels add into every chunk of d_part: zero the chunks nothing has written yet
 static int ensure_all_chunks(nps_ctx *c) {
     if (c->chunks_used < c->n_chunks) {
-        HIP_TRY(hipMemsetAsync(c->d_part + (uint64_t)c->chunks_used * c->geom.part_chunk_stride, 0,
+        HIP_TRY(hipMemsetAsync(c->d_part.get() + (uint64_t)c->chunks_used * c->geom.part_chunk_stride, 0,
                                sizeof(double) * (c->n_chunks - c->chunks_used) * c->geom.part_chunk_stride,
-                               c->stream));
+                               c->stream.get()));
         c->chunks_used = c->n_chunks;
     }
     return NPS_OK;
@@ -455,7 +401,8 @@ extern "C" int nps_create(nps_ctx **out, int device, uint64_t n_samples, const n
                     (unsigned long long)n_samples);
     rc = select_device(device);
     if (rc) return rc;
-    nps_ctx *c = new (std::nothrow) nps_ctx;
+    std::unique_ptr<nps_ctx> owner(new (std::nothrow) nps_ctx);
+    nps_ctx *c = owner.get();
     if (!c) return fail(NPS_E_NOMEM, "out of host memory");
     c->device = device;
     c->n = n_samples;
@@ -464,29 +411,19 @@ extern "C" int nps_create(nps_ctx **out, int device, uint64_t n_samples, const n
     c->params = *params;
     choose_geometry(c);
 
-    const uint64_t row_bytes = c->stride_words * 4;
-    uint64_t cap = (64ull << 20) / row_bytes;
+    const uint64_t row_words = c->stride_words;
+    uint64_t cap = (64ull << 20) / (row_words * 4);
     cap = std::max<uint64_t>(16, std::min<uint64_t>(cap, 4096));
     cap = cap / 16 * 16;
     c->batch_cap = (uint32_t)cap;
     c->geom.groups_per_chunk =
         std::max(1u, ((c->batch_cap / 4) + c->n_chunks - 1) / c->n_chunks);
 
-#define CTX_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            int code = fail(_e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP,         \
-                            "%s failed: %s", #expr, hipGetErrorString(_e));              \
-            free_ctx(c);                                                                 \
-            return code;                                                                 \
-        }                                                                                \
-    } while (0)
-    CTX_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    CTX_TRY(hipMalloc(&c->d_codes, row_bytes * c->batch_cap));
-    CTX_TRY(hipMemsetAsync(c->d_codes, 0, row_bytes * c->batch_cap, c->stream));
-    CTX_TRY(hipMalloc(&c->d_tally, sizeof(unsigned long long) * c->batch_cap));
-    CTX_TRY(hipMalloc(&c->d_desc, sizeof(nps_row_desc) * c->batch_cap));
+    HIP_TRY(c->stream.create());
+    HIP_TRY(c->d_codes.alloc(row_words * c->batch_cap));
+    HIP_TRY(hipMemsetAsync(c->d_codes.get(), 0, row_words * 4 * c->batch_cap, c->stream.get()));
+    HIP_TRY(c->d_tally.alloc(c->batch_cap));
+    HIP_TRY(c->d_desc.alloc(c->batch_cap));
     {
         // One pinned arena for all host staging, carved at 4 KiB boundaries, padded to 64 KiB.
         auto up = [](size_t v) { return (v + 4095) / 4096 * 4096; };
@@ -495,8 +432,8 @@ extern "C" int nps_create(nps_ctx **out, int device, uint64_t n_samples, const n
         const size_t sz_raw = up(sizeof(int32_t) * 2 * std::max<uint64_t>(c->n, 1));
         size_t total = 4096 + sz_desc + sz_stats + nps_ctx::kRawSlots * sz_raw;
         total = (total + 65535) / 65536 * 65536;
-        CTX_TRY(hipHostMalloc(&c->h_arena, total));
-        char *p = (char *)c->h_arena;
+        HIP_TRY(c->h_arena.alloc(total));
+        char *p = (char *)c->h_arena.get();
         c->h_result = (unsigned long long *)p;
         c->h_result[0] = c->h_result[1] = c->h_result[2] = 0;
         p += 4096;
@@ -509,28 +446,22 @@ extern "C" int nps_create(nps_ctx **out, int device, uint64_t n_samples, const n
             p += sz_raw;
         }
     }
-    CTX_TRY(hipMalloc(&c->d_lut, sizeof(double) * 4 * c->batch_cap));
-    CTX_TRY(hipMalloc(&c->d_stats, sizeof(nps_locus_stat) * c->batch_cap));
-    for (int k = 0; k < nps_ctx::kRawSlots; ++k) {
-        CTX_TRY(hipEventCreateWithFlags(&c->ev_raw[k], hipEventDisableTiming));
-    }
-    CTX_TRY(hipMalloc(&c->d_part, sizeof(double) * c->n_chunks * c->geom.part_chunk_stride));
-    CTX_TRY(hipMalloc(&c->d_scores, sizeof(double) * std::max<uint64_t>(c->n, 1)));
-    CTX_TRY(hipMalloc(&c->d_nloci, 256));
-    CTX_TRY(hipMalloc(&c->d_timeout, 256));
-    CTX_TRY(hipMemsetAsync(c->d_timeout, 0, 256, c->stream));
-    CTX_TRY(hipMemsetAsync(c->d_tally, 0, sizeof(unsigned long long) * c->batch_cap, c->stream));
-#undef CTX_TRY
+    HIP_TRY(c->d_lut.alloc(4ull * c->batch_cap));
+    HIP_TRY(c->d_stats.alloc(c->batch_cap));
+    for (int k = 0; k < nps_ctx::kRawSlots; ++k) HIP_TRY(c->ev_raw[k].create(hipEventDisableTiming));
+    HIP_TRY(c->d_part.alloc(c->n_chunks * c->geom.part_chunk_stride));
+    HIP_TRY(c->d_scores.alloc(std::max<uint64_t>(c->n, 1)));
+    HIP_TRY(c->d_nloci.alloc(256 / sizeof(unsigned long long)));
+    HIP_TRY(c->d_timeout.alloc(256 / sizeof(unsigned int)));
+    HIP_TRY(hipMemsetAsync(c->d_timeout.get(), 0, 256, c->stream.get()));
+    HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->batch_cap, c->stream.get()));
     rc = zero_state(c);
-    if (rc) {
-        free_ctx(c);
-        return rc;
-    }
-    *out = c;
+    if (rc) return rc;
+    *out = owner.release();
     return NPS_OK;
 }
 
-extern "C" void nps_destroy(nps_ctx *ctx) { free_ctx(ctx); }
+extern "C" void nps_destroy(nps_ctx *ctx) { delete ctx; }
 extern "C" uint64_t nps_n_samples(const nps_ctx *ctx) { return ctx ? ctx->n : 0; }
 extern "C" int nps_device(const nps_ctx *ctx) { return ctx ? ctx->device : -1; }
 
@@ -606,49 +537,49 @@ static int run_batch(nps_ctx *c) {
     const uint32_t rows = c->batch_rows;
     if (rows) {
         const uint32_t rows_pad = (rows + 3) / 4 * 4;
-        HIP_TRY(hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(nps_row_desc) * rows,
-                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_desc.get(), c->h_desc, sizeof(nps_row_desc) * rows,
+                               hipMemcpyHostToDevice, c->stream.get()));
         {
             ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_row_params(c->stream, c->d_tally, c->d_desc, rows, rows_pad, c->n,
-                                      dev_params(c->params), c->d_lut, c->d_stats, c->d_nloci));
+            HIP_TRY(launch_row_params(c->stream.get(), c->d_tally.get(), c->d_desc.get(), rows, rows_pad, c->n,
+                                      dev_params(c->params), c->d_lut.get(), c->d_stats.get(), c->d_nloci.get()));
         }
         if (c->n) {
             int rc = ensure_all_chunks(c);
             if (rc) return rc;
             ProfScope ps(c, P_ACCUM);
-            HIP_TRY(launch_accumulate(c->stream, c->d_codes, c->stride_words, rows, c->d_lut, c->geom,
-                                      c->d_part));
+            HIP_TRY(launch_accumulate(c->stream.get(), c->d_codes.get(), c->stride_words, rows, c->d_lut.get(), c->geom,
+                                      c->d_part.get()));
         }
-        HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats, sizeof(nps_locus_stat) * rows,
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_tally, 0, sizeof(unsigned long long) * rows, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats.get(), sizeof(nps_locus_stat) * rows,
+                               hipMemcpyDeviceToHost, c->stream.get()));
+        HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * rows, c->stream.get()));
     }
     const uint32_t drows = c->ds_rows;
     if (drows) {
-        HIP_TRY(hipMemcpyAsync(c->d_ds_desc, c->h_ds_desc, sizeof(nps_row_desc) * drows,
-                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_ds_desc.get(), c->h_ds_desc, sizeof(nps_row_desc) * drows,
+                               hipMemcpyHostToDevice, c->stream.get()));
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_ds_tally(c->stream, c->d_ds, c->ds_stride_f, c->n, c->d_ds_desc, drows,
-                                    c->d_ds_tally));
+            HIP_TRY(launch_ds_tally(c->stream.get(), c->d_ds.get(), c->ds_stride_f, c->n, c->d_ds_desc.get(), drows,
+                                    c->d_ds_tally.get()));
         }
         {
             ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_ds_params(c->stream, c->d_ds_tally, c->d_ds_desc, drows, c->n,
-                                     dev_params(c->params), c->d_ds_rowp, c->d_ds_stats, c->d_nloci));
+            HIP_TRY(launch_ds_params(c->stream.get(), c->d_ds_tally.get(), c->d_ds_desc.get(), drows, c->n,
+                                     dev_params(c->params), c->d_ds_rowp.get(), c->d_ds_stats.get(), c->d_nloci.get()));
         }
         {
             int rc = ensure_all_chunks(c);
             if (rc) return rc;
             ProfScope ps(c, P_ACCUM);
-            HIP_TRY(launch_ds_accumulate(c->stream, c->d_ds, c->ds_stride_f, c->n, c->d_ds_rowp, drows,
-                                         c->d_part, c->n_chunks, c->geom.part_chunk_stride));
+            HIP_TRY(launch_ds_accumulate(c->stream.get(), c->d_ds.get(), c->ds_stride_f, c->n, c->d_ds_rowp.get(), drows,
+                                         c->d_part.get(), c->n_chunks, c->geom.part_chunk_stride));
         }
-        HIP_TRY(hipMemcpyAsync(c->h_ds_stats, c->d_ds_stats, sizeof(nps_locus_stat) * drows,
-                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_ds_stats, c->d_ds_stats.get(), sizeof(nps_locus_stat) * drows,
+                               hipMemcpyDeviceToHost, c->stream.get()));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     for (auto &p : c->pending)
         c->ready.push_back(p.batch_idx < 0 ? p.host
                                            : (p.is_ds ? c->h_ds_stats[p.batch_idx] : c->h_stats[p.batch_idx]));
@@ -704,30 +635,26 @@ static int push_gt_polyploid(nps_ctx *c, const void *gts, int elem_bytes, int pl
     d.ref_is_effect = (ref_is_effect ? 1 : 0) | 2;
     if (c->n) {
         const size_t bytes = (size_t)elem_bytes * (size_t)ploidy * c->n;
-        if (bytes > c->poly_cap) {  // the staging grows to the widest record seen (rare: once per context)
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->poly_cap = 0;
+        if (bytes > c->h_poly[1].cap()) {  // the staging grows to the widest record seen (rare: once per context)
+            HIP_TRY(hipStreamSynchronize(c->stream.get()));
             for (int k = 0; k < 2; ++k) {
-                (void)hipHostFree(c->h_poly[k]);
-                c->h_poly[k] = nullptr;
-                if (!c->ev_poly[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_poly[k], hipEventDisableTiming));
+                c->h_poly[k].reset();
+                if (!c->ev_poly[k].get()) HIP_TRY(c->ev_poly[k].create(hipEventDisableTiming));
             }
-            HIP_TRY(hipHostMalloc(&c->h_poly[0], bytes));
-            HIP_TRY(hipHostMalloc(&c->h_poly[1], bytes));
-            c->poly_cap = bytes;
+            for (int k = 0; k < 2; ++k) HIP_TRY(c->h_poly[k].alloc(bytes));  // ([1] last: its size is the ring's)
         }
         // as for diploid rows: the caller may reuse `gts` on return, so it is copied into a pinned ring
         // slot first (which the decode kernel reads where it lies); no stream synchronisation per row
         const int k = c->poly_next;
         c->poly_next ^= 1;
-        HIP_TRY(hipEventSynchronize(c->ev_poly[k]));
-        memcpy(c->h_poly[k], gts, bytes);
+        HIP_TRY(hipEventSynchronize(c->ev_poly[k].get()));
+        memcpy(c->h_poly[k].get(), gts, bytes);
         {
             ProfScope ps(c, P_DECODE);
-            HIP_TRY(launch_decode_gt_to_ds(c->stream, c->h_poly[k], elem_bytes, c->n, ploidy, eaidx,
-                                           c->d_ds + (uint64_t)slot * c->ds_stride_f));
+            HIP_TRY(launch_decode_gt_to_ds(c->stream.get(), c->h_poly[k].get(), elem_bytes, c->n, ploidy, eaidx,
+                                           c->d_ds.get() + (uint64_t)slot * c->ds_stride_f));
         }
-        HIP_TRY(hipEventRecord(c->ev_poly[k], c->stream));
+        HIP_TRY(hipEventRecord(c->ev_poly[k].get(), c->stream.get()));
     }
     PendingRow p;
     p.batch_idx = (int32_t)slot;
@@ -757,18 +684,18 @@ static int push_gt_typed(nps_ctx *c, const void *gts, int elem_bytes, int ploidy
         // the caller may reuse `gts` on return: copy it into a pinned ring slot first
         const int k = c->raw_next;
         c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k]));
+        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
         const size_t bytes = (size_t)elem_bytes * (size_t)ploidy * c->n;
         memcpy(c->h_raw[k], gts, bytes);
         // the decode kernel reads the pinned slot itself, over PCIe: one launch per row instead of a DMA
         // copy and a launch that wait for each other (copy engine <-> compute queue, ~50 us per row)
         {
             ProfScope ps(c, P_DECODE);
-            HIP_TRY(launch_decode_gt(c->stream, c->h_raw[k], elem_bytes, c->n, ploidy, eaidx,
-                                     c->d_codes + (uint64_t)(slot >> 2) * c->stride_words * 4, slot & 3,
-                                     c->d_tally + slot));
+            HIP_TRY(launch_decode_gt(c->stream.get(), c->h_raw[k], elem_bytes, c->n, ploidy, eaidx,
+                                     c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4, slot & 3,
+                                     c->d_tally.get() + slot));
         }
-        HIP_TRY(hipEventRecord(c->ev_raw[k], c->stream));
+        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
     }
     commit_data_row(c, slot);
     return NPS_OK;
@@ -795,15 +722,15 @@ extern "C" int nps_push_packed(nps_ctx *c, const uint32_t *row, int ref_is_effec
     if (c->n) {
         const int k = c->raw_next;
         c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k]));
+        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
         memcpy(c->h_raw[k], row, sizeof(uint32_t) * c->n_words);
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_scatter_row(c->stream, reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n, -1,
-                                             c->d_codes + (uint64_t)(slot >> 2) * c->stride_words * 4,
-                                             slot & 3, c->d_tally + slot));
+            HIP_TRY(launch_tally_scatter_row(c->stream.get(), reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n, -1,
+                                             c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4,
+                                             slot & 3, c->d_tally.get() + slot));
         }
-        HIP_TRY(hipEventRecord(c->ev_raw[k], c->stream));
+        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
     }
     commit_data_row(c, slot);
     return NPS_OK;
@@ -821,18 +748,18 @@ extern "C" int nps_push_bed(nps_ctx *c, const uint8_t *bed_row, int effect_is_a1
     if (c->n) {
         const int k = c->raw_next;
         c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k]));
+        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
         const size_t bytes = (size_t)((c->n + 3) / 4), padded = sizeof(uint32_t) * c->n_words;
         memcpy(c->h_raw[k], bed_row, bytes);
         memset((char *)c->h_raw[k] + bytes, 0, padded - bytes);
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_scatter_row(c->stream, reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n,
+            HIP_TRY(launch_tally_scatter_row(c->stream.get(), reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n,
                                              effect_is_a1,
-                                             c->d_codes + (uint64_t)(slot >> 2) * c->stride_words * 4,
-                                             slot & 3, c->d_tally + slot));
+                                             c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4,
+                                             slot & 3, c->d_tally.get() + slot));
         }
-        HIP_TRY(hipEventRecord(c->ev_raw[k], c->stream));
+        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
     }
     commit_data_row(c, slot);
     return NPS_OK;
@@ -840,24 +767,24 @@ extern "C" int nps_push_bed(nps_ctx *c, const uint8_t *bed_row, int effect_is_a1
 
 // lazily allocate the DS streaming batch
 static int ensure_ds(nps_ctx *c) {
-    if (c->d_ds) return NPS_OK;
+    if (c->ev_ds_raw[1].get()) return NPS_OK;  // (created last: the batch is complete)
     c->ds_stride_f = ds_stride_floats(c->n);
     const uint64_t row_bytes = c->ds_stride_f * 4;
     uint64_t cap = (64ull << 20) / row_bytes;
     cap = std::max<uint64_t>(4, std::min<uint64_t>(cap, 1024));
     c->ds_cap = (uint32_t)cap;
-    HIP_TRY(hipMalloc(&c->d_ds, row_bytes * cap));
-    HIP_TRY(hipMemsetAsync(c->d_ds, 0, row_bytes * cap, c->stream));
-    HIP_TRY(hipMalloc(&c->d_ds_desc, sizeof(nps_row_desc) * cap));
-    HIP_TRY(hipMalloc(&c->d_ds_tally, sizeof(DsTally) * cap));
-    HIP_TRY(hipMalloc(&c->d_ds_rowp, sizeof(DsRowP) * cap));
-    HIP_TRY(hipMalloc(&c->d_ds_stats, sizeof(nps_locus_stat) * cap));
+    HIP_TRY(c->d_ds.alloc(c->ds_stride_f * cap));
+    HIP_TRY(hipMemsetAsync(c->d_ds.get(), 0, row_bytes * cap, c->stream.get()));
+    HIP_TRY(c->d_ds_desc.alloc(cap));
+    HIP_TRY(c->d_ds_tally.alloc(cap));
+    HIP_TRY(c->d_ds_rowp.alloc(cap));
+    HIP_TRY(c->d_ds_stats.alloc(cap));
     auto up = [](size_t v) { return (v + 4095) / 4096 * 4096; };
     const size_t sz_desc = up(sizeof(nps_row_desc) * cap), sz_stats = up(sizeof(nps_locus_stat) * cap);
     const size_t sz_raw = up(sizeof(float) * std::max<uint64_t>(c->n, 1));
     size_t total = (sz_desc + sz_stats + 2 * sz_raw + 65535) / 65536 * 65536;
-    HIP_TRY(hipHostMalloc(&c->h_ds_arena, total));
-    char *p = (char *)c->h_ds_arena;
+    HIP_TRY(c->h_ds_arena.alloc(total));
+    char *p = (char *)c->h_ds_arena.get();
     c->h_ds_desc = (nps_row_desc *)p;
     p += sz_desc;
     c->h_ds_stats = (nps_locus_stat *)p;
@@ -865,7 +792,7 @@ static int ensure_ds(nps_ctx *c) {
     for (int k = 0; k < 2; ++k) {
         c->h_ds_raw[k] = (float *)p;
         p += sz_raw;
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_ds_raw[k], hipEventDisableTiming));
+        if (!c->ev_ds_raw[k].get()) HIP_TRY(c->ev_ds_raw[k].create(hipEventDisableTiming));
     }
     return NPS_OK;
 }
@@ -889,11 +816,11 @@ extern "C" int nps_push_ds(nps_ctx *c, const float *ds, int ref_is_effect, doubl
     if (c->n) {
         const int k = c->ds_raw_next;
         c->ds_raw_next = (k + 1) % 2;
-        HIP_TRY(hipEventSynchronize(c->ev_ds_raw[k]));
+        HIP_TRY(hipEventSynchronize(c->ev_ds_raw[k].get()));
         memcpy(c->h_ds_raw[k], ds, sizeof(float) * c->n);
-        HIP_TRY(hipMemcpyAsync(c->d_ds + (uint64_t)slot * c->ds_stride_f, c->h_ds_raw[k],
-                               sizeof(float) * c->n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_ds_raw[k], c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_ds.get() + (uint64_t)slot * c->ds_stride_f, c->h_ds_raw[k],
+                               sizeof(float) * c->n, hipMemcpyHostToDevice, c->stream.get()));
+        HIP_TRY(hipEventRecord(c->ev_ds_raw[k].get(), c->stream.get()));
     }
     PendingRow p;
     p.batch_idx = (int32_t)slot;
@@ -918,8 +845,8 @@ extern "C" int nps_push_locus(nps_ctx *c, int kind, int ref_is_effect, double be
 
 // the device's result block (used rows, status bits) -> pinned host copy; the caller synchronises
 static int fetch_result(nps_ctx *c) {
-    HIP_TRY(hipMemcpyAsync(c->h_result, c->d_nloci, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                           c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_result, c->d_nloci.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           c->stream.get()));
     return NPS_OK;
 }
 
@@ -942,7 +869,7 @@ extern "C" int nps_flush(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size
     if (rc) return rc;
     rc = fetch_result(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     rc = check_status(c);
     if (rc) return rc;
     size_t n = 0;
@@ -966,14 +893,14 @@ static int finish_common(nps_ctx *c, double offset, double *d_dst, double *h_sco
     if (rc) return rc;
     if (c->n) {
         ProfScope ps(c, P_REDUCE);
-        HIP_TRY(launch_finish(c->stream, c->d_part, c->chunks_used, c->geom.part_chunk_stride, c->n,
-                              c->const_sum, c->d_nloci, c->host_nloci, normalise ? 1 : 0, offset, d_dst));
+        HIP_TRY(launch_finish(c->stream.get(), c->d_part.get(), c->chunks_used, c->geom.part_chunk_stride, c->n,
+                              c->const_sum, c->d_nloci.get(), c->host_nloci, normalise ? 1 : 0, offset, d_dst));
     }
     rc = fetch_result(c);
     if (rc) return rc;
     if (h_scores_out && c->n)
-        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     rc = check_status(c);
     if (rc) return rc;
     if (nloci_out) *nloci_out = c->host_nloci + c->h_result[0];
@@ -985,7 +912,7 @@ extern "C" int nps_finish(nps_ctx *c, double offset, double *scores_out, uint64_
     if (rc) return rc;
     if (c->n && !scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    return finish_common(c, offset, c->d_scores, scores_out, nloci_out);
+    return finish_common(c, offset, c->d_scores.get(), scores_out, nloci_out);
 }
 
 extern "C" int nps_finish_device(nps_ctx *c, double offset, double *d_scores_out,
@@ -1012,9 +939,9 @@ extern "C" int nps_normalize_device(nps_ctx *c, double *d_sums, uint64_t nloci, 
     if (c->n) {
         // one "chunk" = the reduced sums themselves, in place (every thread reads and writes its own i)
         ProfScope ps(c, P_REDUCE);
-        HIP_TRY(launch_finish(c->stream, d_sums, 1, c->n, c->n, 0.0, nullptr, nloci, 1, offset, d_sums));
+        HIP_TRY(launch_finish(c->stream.get(), d_sums, 1, c->n, c->n, 0.0, nullptr, nloci, 1, offset, d_sums));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     return NPS_OK;
 }
 
@@ -1040,7 +967,8 @@ extern "C" int nps_cohort_create(nps_cohort **out, int device, uint64_t n_sample
         // the row layout, whose table-lookup kernel runs at 0.47 .. 0.63 of the roofline depending on the genotypes.)
         format = n_samples < (1ull << 27) ? NPS_FMT_GT2X : NPS_FMT_GT2;
     }
-    nps_cohort *c = new (std::nothrow) nps_cohort;
+    std::unique_ptr<nps_cohort> owner(new (std::nothrow) nps_cohort);
+    nps_cohort *c = owner.get();
     if (!c) return fail(NPS_E_NOMEM, "out of host memory");
     c->device = device;
     c->format = format;
@@ -1054,39 +982,26 @@ extern "C" int nps_cohort_create(nps_cohort **out, int device, uint64_t n_sample
     if (format == NPS_FMT_GT2M) {
         c->stride_bytes = 0;  // not row-major: 1 KiB units of 128 rows x 32 samples
         bytes = std::max<uint64_t>(gt2m_bytes(n_samples, n_rows), 256);
-        const uint64_t tb = sizeof(unsigned long long) * std::max<uint64_t>(gt2m_superblocks(n_rows) * 128, 1);
-        if (hipMalloc(&c->d_row_tally, tb) != hipSuccess || hipMemset(c->d_row_tally, 0, tb) != hipSuccess) {
-            (void)hipFree(c->d_row_tally);
-            delete c;
+        const uint64_t words = std::max<uint64_t>(gt2m_superblocks(n_rows) * 128, 1);
+        if (c->d_row_tally.alloc(words) != hipSuccess ||
+            hipMemset(c->d_row_tally.get(), 0, sizeof(unsigned long long) * words) != hipSuccess)
             return fail(NPS_E_NOMEM, "hipMalloc of the row tallies failed");
-        }
     }
     if (format == NPS_FMT_GT2X) {
         c->stride_bytes = 0;  // not row-major: strips x superblocks x 1 KiB units
         bytes = std::max<uint64_t>(gt2x_bytes(n_samples, n_rows), 256);
         const uint64_t words = (gt2x_superblocks(n_rows) + 63) / 64;
         c->mx_sb_valid.reset(new (std::nothrow) std::atomic<uint64_t>[std::max<uint64_t>(words, 1)]);
-        if (!c->mx_sb_valid) {
-            delete c;
-            return fail(NPS_E_NOMEM, "out of host memory");
-        }
+        if (!c->mx_sb_valid) return fail(NPS_E_NOMEM, "out of host memory");
         for (uint64_t w = 0; w < std::max<uint64_t>(words, 1); ++w) c->mx_sb_valid[w].store(0, std::memory_order_relaxed);
     }
-    hipError_t e = hipMalloc(&c->d_data, bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_row_tally);
-        delete c;
-        return fail(NPS_E_NOMEM, "hipMalloc(%llu bytes) for the cohort failed: %s",
+    hipError_t e = c->d_data.alloc(bytes);
+    if (e != hipSuccess)
+        return fail(NPS_E_NOMEM, "allocating %llu bytes for the cohort failed: %s",
                     (unsigned long long)bytes, hipGetErrorString(e));
-    }
-    e = hipMemset(c->d_data, 0, bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_data);
-        (void)hipFree(c->d_row_tally);
-        delete c;
-        return fail(NPS_E_HIP, "hipMemset failed: %s", hipGetErrorString(e));
-    }
-    *out = c;
+    e = hipMemset(c->d_data.get(), 0, bytes);
+    if (e != hipSuccess) return fail(NPS_E_HIP, "hipMemset failed: %s", hipGetErrorString(e));
+    *out = owner.release();
     return NPS_OK;
 }
 
@@ -1094,26 +1009,12 @@ extern "C" uint64_t nps_cohort_row_stride(const nps_cohort *c) { return c ? c->s
 extern "C" uint64_t nps_cohort_n_rows(const nps_cohort *c) { return c ? c->n_rows : 0; }
 extern "C" int nps_cohort_format(const nps_cohort *c) { return c ? c->format : -1; }
 
-extern "C" void nps_cohort_destroy(nps_cohort *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(c->d_data);
-    (void)hipFree(c->d_row_tally);
-    (void)hipFree(c->d_mx_row_tally);
-    (void)hipFree(c->d_push_tally);
-    for (int k = 0; k < 2; ++k) {
-        (void)hipHostFree(c->h_push[k]);
-        if (c->ev_push[k]) (void)hipEventDestroy(c->ev_push[k]);
-    }
-    if (c->push_stream) (void)hipStreamDestroy(c->push_stream);
-    delete c;
-}
+extern "C" void nps_cohort_destroy(nps_cohort *c) { delete c; }
 
 // back to the plain layout (before rows are written into an optimised cohort); the transform is its own inverse
 static int cohort_unoptimize(nps_cohort *c) {
     if (!c->optimized) return NPS_OK;
-    hipError_t e = launch_cohort_parity(nullptr, (uint32_t *)c->d_data, c->stride_bytes / 4, c->n_samples, c->n_rows);
+    hipError_t e = launch_cohort_parity(nullptr, (uint32_t *)c->d_data.get(), c->stride_bytes / 4, c->n_samples, c->n_rows);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(NPS_E_HIP, "cohort re-ordering failed: %s", hipGetErrorString(e));
     c->optimized = false;
@@ -1125,7 +1026,7 @@ extern "C" int nps_cohort_optimize(nps_cohort *c) {
     if (c->format != NPS_FMT_GT2 || c->optimized || c->n_rows == 0 || c->n_samples == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // no scoring kernel may still be reading the rows rewritten here
-    hipError_t e = launch_cohort_parity(nullptr, (uint32_t *)c->d_data, c->stride_bytes / 4, c->n_samples, c->n_rows);
+    hipError_t e = launch_cohort_parity(nullptr, (uint32_t *)c->d_data.get(), c->stride_bytes / 4, c->n_samples, c->n_rows);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(NPS_E_HIP, "cohort optimisation failed: %s", hipGetErrorString(e));
     c->optimized = true;
@@ -1151,7 +1052,7 @@ static int gt2_transfer(const nps_cohort *c, uint64_t row0, uint64_t nrows, void
     for (uint64_t r = 0; r < nrows; r += chunk_groups * 4) {
         const uint64_t k = std::min<uint64_t>(chunk_groups * 4, nrows - r);  // rows in this chunk
         const uint64_t groups = (k + 3) / 4;
-        char *dev = (char *)c->d_data + ((row0 + r) >> 2) * sw * 16;
+        char *dev = (char *)c->d_data.get() + ((row0 + r) >> 2) * sw * 16;
         buf.assign(groups * sw * 4, 0u);
         if (!to_device) {
             HIP_TRY(hipMemcpy(buf.data(), dev, groups * sw * 16, hipMemcpyDeviceToHost));
@@ -1186,27 +1087,20 @@ static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *
     uint64_t chunk = std::max<uint64_t>(4, (256ull << 20) / (src_stride_words * 4)) / 4 * 4;
     chunk = std::min<uint64_t>(chunk, 4ull * 65535);
     chunk = std::min<uint64_t>(chunk, (nrows + 3) / 4 * 4);
-    uint32_t *d_stage = nullptr;
-    uint8_t *d_mode = nullptr;
-    HIP_TRY(hipMalloc(&d_stage, chunk * src_stride_words * 4));
-    hipError_t e = hipSuccess;
-    if (bed_mode) e = hipMalloc(&d_mode, chunk);
-    for (uint64_t r = 0; e == hipSuccess && r < nrows; r += chunk) {
+    DevBuf<uint32_t> d_stage;
+    DevBuf<uint8_t> d_mode;
+    HIP_TRY(d_stage.alloc(chunk * src_stride_words));
+    if (bed_mode) HIP_TRY(d_mode.alloc(chunk));
+    for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        e = hipMemsetAsync(d_stage, 0, chunk * src_stride_words * 4, nullptr);
-        if (e == hipSuccess)
-            e = hipMemcpy2D(d_stage, src_stride_words * 4, (const char *)host_rows + r * host_stride,
-                            host_stride, width, k, hipMemcpyHostToDevice);
-        if (e == hipSuccess && bed_mode) e = hipMemcpy(d_mode, bed_mode + r, k, hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = launch_interleave_rows(nullptr, d_stage, src_stride_words, k, c->n_samples,
-                                       bed_mode ? d_mode : nullptr,
-                                       (uint32_t *)((char *)c->d_data + ((row0 + r) >> 2) * sw * 16), sw);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
+        HIP_TRY(hipMemsetAsync(d_stage.get(), 0, chunk * src_stride_words * 4, nullptr));
+        HIP_TRY(hipMemcpy2D(d_stage.get(), src_stride_words * 4, (const char *)host_rows + r * host_stride,
+                            host_stride, width, k, hipMemcpyHostToDevice));
+        if (bed_mode) HIP_TRY(hipMemcpy(d_mode.get(), bed_mode + r, k, hipMemcpyHostToDevice));
+        HIP_TRY(launch_interleave_rows(nullptr, d_stage.get(), src_stride_words, k, c->n_samples, d_mode.get(),
+                                       (uint32_t *)(c->d_data.get() + ((row0 + r) >> 2) * sw * 16), sw));
+        HIP_TRY(hipDeviceSynchronize());
     }
-    (void)hipFree(d_stage);
-    (void)hipFree(d_mode);
-    if (e != hipSuccess) return fail(NPS_E_HIP, "cohort upload failed: %s", hipGetErrorString(e));
     return NPS_OK;
 }
 
@@ -1214,18 +1108,14 @@ static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *
 static int gt2x_download(const nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows, size_t host_stride) {
     const uint64_t n_words = words_for(c->n_samples), sw = (n_words + 3) / 4 * 4;
     const uint64_t chunk = std::max<uint64_t>(128, (256ull << 20) / (sw * 4) / 128 * 128);
-    uint32_t *d_stage = nullptr;
-    HIP_TRY(hipMalloc(&d_stage, std::min(chunk, (nrows + 127) / 128 * 128) * sw * 4));
-    hipError_t e = hipSuccess;
-    for (uint64_t r = 0; e == hipSuccess && r < nrows; r += chunk) {
+    DevBuf<uint32_t> d_stage;
+    HIP_TRY(d_stage.alloc(std::min(chunk, (nrows + 127) / 128 * 128) * sw));
+    for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        e = launch_gt2x_to_rows(nullptr, c->d_data, c->n_samples, c->n_rows, row0 + r, k, d_stage, sw);
-        if (e == hipSuccess)
-            e = hipMemcpy2D((char *)host_rows + r * host_stride, host_stride, d_stage, sw * 4, n_words * 4, k,
-                            hipMemcpyDeviceToHost);
+        HIP_TRY(launch_gt2x_to_rows(nullptr, c->d_data.get(), c->n_samples, c->n_rows, row0 + r, k, d_stage.get(), sw));
+        HIP_TRY(hipMemcpy2D((char *)host_rows + r * host_stride, host_stride, d_stage.get(), sw * 4, n_words * 4, k,
+                            hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_stage);
-    if (e != hipSuccess) return fail(NPS_E_HIP, "cohort transfer failed: %s", hipGetErrorString(e));
     return NPS_OK;
 }
 
@@ -1244,24 +1134,20 @@ static int gt2x_fill(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *h
     std::lock_guard<std::mutex> lk(c->tally_mutex);
     HIP_TRY(mx_tallies_alloc(c));
     const uint64_t sb0 = row0 >> 7, n_sb = (nrows + 127) / 128;
-    uint32_t *d_stage = nullptr;
-    uint8_t *d_map = nullptr;
-    HIP_TRY(hipMalloc(&d_stage, std::min(chunk, n_sb * 128) * sw * 4));
-    hipError_t e = hipSuccess;
-    if (code_map) e = hipMalloc(&d_map, std::min(chunk, nrows));
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_mx_row_tally + sb0 * 128, 0, sizeof(unsigned long long) * n_sb * 128, nullptr);
-    for (uint64_t r = 0; e == hipSuccess && r < nrows; r += chunk) {
+    DevBuf<uint32_t> d_stage;
+    DevBuf<uint8_t> d_map;
+    HIP_TRY(d_stage.alloc(std::min(chunk, n_sb * 128) * sw));
+    if (code_map) HIP_TRY(d_map.alloc(std::min(chunk, nrows)));
+    HIP_TRY(hipMemsetAsync(c->d_mx_row_tally.get() + sb0 * 128, 0, sizeof(unsigned long long) * n_sb * 128, nullptr));
+    for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        e = hipMemcpy2D(d_stage, sw * 4, (const char *)host_rows + r * host_stride, host_stride, width, k, hipMemcpyHostToDevice);
-        if (e == hipSuccess && code_map) e = hipMemcpy(d_map, code_map + r, k, hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = launch_fill_gt2x_rows(nullptr, d_stage, sw, d_map, c->n_samples, c->n_rows, row0 + r, k, c->d_data,
-                                      c->d_mx_row_tally);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
+        HIP_TRY(hipMemcpy2D(d_stage.get(), sw * 4, (const char *)host_rows + r * host_stride, host_stride, width, k,
+                            hipMemcpyHostToDevice));
+        if (code_map) HIP_TRY(hipMemcpy(d_map.get(), code_map + r, k, hipMemcpyHostToDevice));
+        HIP_TRY(launch_fill_gt2x_rows(nullptr, d_stage.get(), sw, d_map.get(), c->n_samples, c->n_rows, row0 + r, k,
+                                      c->d_data.get(), c->d_mx_row_tally.get()));
+        HIP_TRY(hipDeviceSynchronize());
     }
-    (void)hipFree(d_stage);
-    (void)hipFree(d_map);
-    if (e != hipSuccess) return fail(NPS_E_HIP, "cohort transfer failed: %s", hipGetErrorString(e));
     mx_tallies_mark(c, sb0, n_sb, true);
     return NPS_OK;
 }
@@ -1296,33 +1182,30 @@ static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes, int *s
     if (row >= c->n_rows) return fail(NPS_E_INVAL, "row %llu outside cohort of %llu rows", (unsigned long long)row,
                                       (unsigned long long)c->n_rows);
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->push_stream) {
+    if (!c->push_stream.get()) {
         HIP_TRY(hipDeviceSynchronize());  // whatever wrote or read the cohort before
         int rc = cohort_unoptimize(c);
         if (rc) return rc;
-        HIP_TRY(hipStreamCreateWithFlags(&c->push_stream, hipStreamNonBlocking));
-        HIP_TRY(hipMalloc(&c->d_push_tally, 256));
-        for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&c->ev_push[k], hipEventDisableTiming));
+        HIP_TRY(c->push_stream.create());
+    }
+    if (!c->ev_push[1].get()) {  // (with the stream, on the first push)
+        HIP_TRY(c->d_push_tally.alloc(256 / sizeof(unsigned long long)));
+        for (int k = 0; k < 2; ++k)
+            if (!c->ev_push[k].get()) HIP_TRY(c->ev_push[k].create(hipEventDisableTiming));
     }
     if (c->optimized) {
         HIP_TRY(hipDeviceSynchronize());
         int rc = cohort_unoptimize(c);
         if (rc) return rc;
     }
-    if (bytes > c->push_cap) {
-        HIP_TRY(hipStreamSynchronize(c->push_stream));
-        for (int k = 0; k < 2; ++k) {
-            (void)hipHostFree(c->h_push[k]);
-            c->h_push[k] = nullptr;
-        }
-        c->push_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->h_push[0], bytes));
-        HIP_TRY(hipHostMalloc(&c->h_push[1], bytes));
-        c->push_cap = bytes;
+    if (bytes > c->h_push[1].cap()) {
+        HIP_TRY(hipStreamSynchronize(c->push_stream.get()));
+        for (int k = 0; k < 2; ++k) c->h_push[k].reset();
+        for (int k = 0; k < 2; ++k) HIP_TRY(c->h_push[k].alloc(bytes));  // ([1] last: its size is the ring's)
     }
     *slot = c->push_next;
     c->push_next ^= 1;
-    HIP_TRY(hipEventSynchronize(c->ev_push[*slot]));
+    HIP_TRY(hipEventSynchronize(c->ev_push[*slot].get()));
     return NPS_OK;
 }
 
@@ -1339,11 +1222,11 @@ extern "C" int nps_cohort_push_gt_raw(nps_cohort *c, uint64_t row, const void *g
     int rc = cohort_push_prepare(c, row, std::max<size_t>(bytes, 16), &k);
     if (rc) return rc;
     if (c->n_samples == 0) return NPS_OK;
-    memcpy(c->h_push[k], gt, bytes);
+    memcpy(c->h_push[k].get(), gt, bytes);
     const uint64_t sw = c->stride_bytes / 4;
-    HIP_TRY(launch_decode_gt(c->push_stream, c->h_push[k], elem_bytes, c->n_samples, ploidy, eaidx,
-                             (uint32_t *)c->d_data + (row >> 2) * sw * 4, (int)(row & 3), c->d_push_tally));
-    HIP_TRY(hipEventRecord(c->ev_push[k], c->push_stream));
+    HIP_TRY(launch_decode_gt(c->push_stream.get(), c->h_push[k].get(), elem_bytes, c->n_samples, ploidy, eaidx,
+                             (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3), c->d_push_tally.get()));
+    HIP_TRY(hipEventRecord(c->ev_push[k].get(), c->push_stream.get()));
     return NPS_OK;
 }
 
@@ -1355,13 +1238,13 @@ extern "C" int nps_cohort_push_bed(nps_cohort *c, uint64_t row, const uint8_t *b
     int rc = cohort_push_prepare(c, row, std::max<size_t>((bytes + 3) / 4 * 4 + 16, 16), &k);
     if (rc) return rc;
     if (c->n_samples == 0) return NPS_OK;
-    memset(c->h_push[k], 0, (bytes + 3) / 4 * 4 + 16);
-    memcpy(c->h_push[k], bed_row, bytes);
+    memset(c->h_push[k].get(), 0, (bytes + 3) / 4 * 4 + 16);
+    memcpy(c->h_push[k].get(), bed_row, bytes);
     const uint64_t sw = c->stride_bytes / 4;
-    HIP_TRY(launch_tally_scatter_row(c->push_stream, reinterpret_cast<const uint32_t *>(c->h_push[k]), c->n_samples,
-                                     effect_is_a1, (uint32_t *)c->d_data + (row >> 2) * sw * 4, (int)(row & 3),
-                                     c->d_push_tally));
-    HIP_TRY(hipEventRecord(c->ev_push[k], c->push_stream));
+    HIP_TRY(launch_tally_scatter_row(c->push_stream.get(), reinterpret_cast<const uint32_t *>(c->h_push[k].get()), c->n_samples,
+                                     effect_is_a1, (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3),
+                                     c->d_push_tally.get()));
+    HIP_TRY(hipEventRecord(c->ev_push[k].get(), c->push_stream.get()));
     return NPS_OK;
 }
 
@@ -1371,38 +1254,30 @@ extern "C" int nps_cohort_push_bed(nps_cohort *c, uint64_t row, const uint8_t *b
 static int ds16_transfer(nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows, size_t host_stride, bool upload) {
     const uint64_t stride_f = ds_stride_floats(c->n_samples), stride_e = c->stride_bytes / 2;
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nrows, (256ull << 20) / (stride_f * 4)));
-    float *d_stage = nullptr;
-    unsigned char *d_bad = nullptr;
-    HIP_TRY(hipMalloc(&d_stage, chunk * stride_f * 4));
-    if (hipMalloc(&d_bad, chunk) != hipSuccess) {
-        (void)hipFree(d_stage);
-        return fail(NPS_E_NOMEM, "hipMalloc failed");
-    }
+    DevBuf<float> d_stage;
+    DevBuf<unsigned char> d_bad;
+    HIP_TRY(d_stage.alloc(chunk * stride_f));
+    HIP_TRY(d_bad.alloc(chunk));
     std::vector<unsigned char> bad(chunk);
-    hipError_t e = hipSuccess;
     long long first_bad = -1;
-    for (uint64_t r = 0; r < nrows && e == hipSuccess && first_bad < 0; r += chunk) {
+    for (uint64_t r = 0; r < nrows && first_bad < 0; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        uint16_t *rows = (uint16_t *)c->d_data + (row0 + r) * stride_e;
+        uint16_t *rows = (uint16_t *)c->d_data.get() + (row0 + r) * stride_e;
         char *host = (char *)host_rows + r * host_stride;
         if (upload) {
-            e = hipMemcpy2D(d_stage, stride_f * 4, host, host_stride, c->n_samples * 4, k, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = launch_ds16_pack(nullptr, d_stage, stride_f, c->n_samples, k, rows, stride_e, d_bad);
-            if (e == hipSuccess) e = hipMemcpy(bad.data(), d_bad, k, hipMemcpyDeviceToHost);
-            for (uint64_t j = 0; j < k && e == hipSuccess; ++j)
+            HIP_TRY(hipMemcpy2D(d_stage.get(), stride_f * 4, host, host_stride, c->n_samples * 4, k, hipMemcpyHostToDevice));
+            HIP_TRY(launch_ds16_pack(nullptr, d_stage.get(), stride_f, c->n_samples, k, rows, stride_e, d_bad.get()));
+            HIP_TRY(hipMemcpy(bad.data(), d_bad.get(), k, hipMemcpyDeviceToHost));
+            for (uint64_t j = 0; j < k; ++j)
                 if (bad[j]) {
                     first_bad = (long long)(row0 + r + j);
                     break;
                 }
         } else {
-            e = launch_ds16_unpack(nullptr, rows, stride_e, c->n_samples, k, d_stage, stride_f);
-            if (e == hipSuccess)
-                e = hipMemcpy2D(host, host_stride, d_stage, stride_f * 4, c->n_samples * 4, k, hipMemcpyDeviceToHost);
+            HIP_TRY(launch_ds16_unpack(nullptr, rows, stride_e, c->n_samples, k, d_stage.get(), stride_f));
+            HIP_TRY(hipMemcpy2D(host, host_stride, d_stage.get(), stride_f * 4, c->n_samples * 4, k, hipMemcpyDeviceToHost));
         }
     }
-    (void)hipFree(d_stage);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return fail(NPS_E_HIP, "NPS_FMT_DS16 transfer failed: %s", hipGetErrorString(e));
     if (first_bad >= 0)
         return fail(NPS_E_UNSUPPORTED, "row %lld holds a FORMAT/DS value that is not a decimal with at most four places in "
                     "[0, 2]: NPS_FMT_DS16 stores such values only (losslessly); use a NPS_FMT_DS32 cohort", first_bad);
@@ -1429,17 +1304,15 @@ extern "C" int nps_cohort_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, c
         return gt2_upload(c, row0, nrows, host_rows, host_stride, width, nullptr);
     }
     if (c->format == NPS_FMT_GT2X) return gt2x_fill(c, row0, nrows, host_rows, host_stride, width, nullptr);
-    HIP_TRY(hipMemcpy2D((char *)c->d_data + row0 * c->stride_bytes, c->stride_bytes, host_rows,
+    HIP_TRY(hipMemcpy2D((char *)c->d_data.get() + row0 * c->stride_bytes, c->stride_bytes, host_rows,
                         host_stride, width, nrows, hipMemcpyHostToDevice));
     // the range of a dosage, row by row, where the rows now lie (one read at upload time, none when scoring)
-    unsigned char *d_bad = nullptr;
-    HIP_TRY(hipMalloc(&d_bad, nrows));
+    DevBuf<unsigned char> d_bad;
+    HIP_TRY(d_bad.alloc(nrows));
     std::vector<unsigned char> bad(nrows);
-    hipError_t e = launch_ds_range_check(nullptr, (const float *)c->d_data + row0 * (c->stride_bytes / 4), c->stride_bytes / 4,
-                                         c->n_samples, nrows, d_bad);
-    if (e == hipSuccess) e = hipMemcpy(bad.data(), d_bad, nrows, hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return fail(NPS_E_HIP, "range check of the uploaded dosages failed: %s", hipGetErrorString(e));
+    HIP_TRY(launch_ds_range_check(nullptr, (const float *)c->d_data.get() + row0 * (c->stride_bytes / 4), c->stride_bytes / 4,
+                                  c->n_samples, nrows, d_bad.get()));
+    HIP_TRY(hipMemcpy(bad.data(), d_bad.get(), nrows, hipMemcpyDeviceToHost));
     if (c->ds_row_bad.size() != c->n_rows) c->ds_row_bad.assign(c->n_rows, 0);
     for (uint64_t r = 0; r < nrows; ++r) {
         c->ds_bad_rows += (uint64_t)bad[r] - (uint64_t)c->ds_row_bad[row0 + r];
@@ -1461,7 +1334,7 @@ extern "C" int nps_cohort_download(const nps_cohort *c, uint64_t row0, uint64_t 
     if (c->format == NPS_FMT_DS16) return ds16_transfer(const_cast<nps_cohort *>(c), row0, nrows, host_rows, host_stride, false);
     if (c->format == NPS_FMT_GT2) return gt2_transfer(c, row0, nrows, host_rows, host_stride, false);
     if (c->format == NPS_FMT_GT2X) return gt2x_download(c, row0, nrows, host_rows, host_stride);
-    HIP_TRY(hipMemcpy2D(host_rows, host_stride, (const char *)c->d_data + row0 * c->stride_bytes,
+    HIP_TRY(hipMemcpy2D(host_rows, host_stride, (const char *)c->d_data.get() + row0 * c->stride_bytes,
                         c->stride_bytes, width, nrows, hipMemcpyDeviceToHost));
     return NPS_OK;
 }
@@ -1484,32 +1357,33 @@ extern "C" int nps_cohort_synth_rows(nps_cohort *c, uint64_t row0, uint64_t nrow
     mx_tallies_rewrite(c, row0, nrows);
     rc = cohort_unoptimize(c);
     if (rc) return rc;
-    uint32_t *d_t = nullptr;
-    HIP_TRY(hipMalloc(&d_t, sizeof(uint32_t) * 3 * nrows));
-    hipError_t e = hipMemcpy(d_t, t_het, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_t + nrows, t_hom, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_t + 2 * nrows, t_miss, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice);
+    DevBuf<uint32_t> d_thr;  // the three threshold arrays, one after the other
+    HIP_TRY(d_thr.alloc(3 * nrows));
+    uint32_t *const d_t = d_thr.get();
+    HIP_TRY(hipMemcpy(d_t, t_het, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_t + nrows, t_hom, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_t + 2 * nrows, t_miss, sizeof(uint32_t) * nrows, hipMemcpyHostToDevice));
     const uint64_t step = 32768;
+    hipError_t e = hipSuccess;
     for (uint64_t r = 0; e == hipSuccess && r < nrows; r += step) {
         const uint64_t k = std::min(step, nrows - r);
         if (c->format == NPS_FMT_GT2M)
-            e = launch_synth_gt2m(nullptr, c->d_data, c->n_samples, row0 + r, gen_row0 + r, k, seed, d_t + r,
-                                  d_t + nrows + r, d_t + 2 * nrows + r, c->d_row_tally);
+            e = launch_synth_gt2m(nullptr, c->d_data.get(), c->n_samples, row0 + r, gen_row0 + r, k, seed, d_t + r,
+                                  d_t + nrows + r, d_t + 2 * nrows + r, c->d_row_tally.get());
         else if (c->format == NPS_FMT_GT2X)
-            e = launch_synth_gt2x(nullptr, c->d_data, c->n_samples, c->n_rows, row0 + r, gen_row0 + r, k, seed, d_t + r,
+            e = launch_synth_gt2x(nullptr, c->d_data.get(), c->n_samples, c->n_rows, row0 + r, gen_row0 + r, k, seed, d_t + r,
                                   d_t + nrows + r, d_t + 2 * nrows + r);
         else if (c->format == NPS_FMT_DS16)
-            e = launch_synth_ds16(nullptr, (uint16_t *)c->d_data, c->stride_bytes / 2, c->n_samples, row0 + r, gen_row0 + r, k,
+            e = launch_synth_ds16(nullptr, (uint16_t *)c->d_data.get(), c->stride_bytes / 2, c->n_samples, row0 + r, gen_row0 + r, k,
                                   seed, d_t + r, d_t + nrows + r, d_t + 2 * nrows + r);
         else if (c->format == NPS_FMT_DS32)
-            e = launch_synth_ds(nullptr, (float *)c->d_data, c->stride_bytes / 4, c->n_samples,
+            e = launch_synth_ds(nullptr, (float *)c->d_data.get(), c->stride_bytes / 4, c->n_samples,
                                 row0 + r, gen_row0 + r, k, seed, d_t + r, d_t + nrows + r, d_t + 2 * nrows + r);
         else
-            e = launch_synth_gt(nullptr, (uint32_t *)c->d_data, c->stride_bytes / 4, c->n_samples,
+            e = launch_synth_gt(nullptr, (uint32_t *)c->d_data.get(), c->stride_bytes / 4, c->n_samples,
                                 row0 + r, gen_row0 + r, k, seed, d_t + r, d_t + nrows + r, d_t + 2 * nrows + r);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_t);
     if (e != hipSuccess) return fail(NPS_E_HIP, "synthetic fill failed: %s", hipGetErrorString(e));
     if (c->format == NPS_FMT_DS32 && c->ds_bad_rows)  // the generator clips to [0, 2]: these rows are in range now
         for (uint64_t r = row0; r < row0 + nrows && r < c->ds_row_bad.size(); ++r) {
@@ -1532,7 +1406,7 @@ struct nps_scoredef {
     uint64_t m = 0;                       // PRESENT rows (consume cohort rows)
     std::vector<nps_row_desc> host_rows;  // rows without genotype data, in order
     std::vector<int64_t> data_index;      // per desc: >= 0 index among PRESENT rows, -1 host row
-    nps_row_desc *d_desc = nullptr;       // [m] PRESENT rows, compact
+    DevBuf<nps_row_desc> d_desc;          // [m] PRESENT rows, compact
     // NPS_FMT_GT2X runs: the largest |beta| (4 + max(2, 2 |eaf|)) over the PRESENT rows with finite numbers: the
     // fixed-point scale 2^F of fused_mx_kernel keeps every weight below 2^56
     double mx_bound = 0.0;
@@ -1541,16 +1415,24 @@ struct nps_scoredef {
     // outside the band, scored one pass per band with the band's own scale (empty: one band, d_desc itself)
     struct MxBand {
         double bound = 0.0;
-        nps_row_desc *d_desc = nullptr;
+        DevBuf<nps_row_desc> d_desc;
     };
     std::vector<MxBand> mx_bands;
     // ... and the PRESENT rows those kernels cannot carry (mx_special): their indices among the PRESENT rows, ascending,
     // and their descriptors as given.  d_mx_desc is d_desc with these rows at beta = eaf = 0 (null: no special row);
     // after the fixed-point pass mx_special_pass adds their products in IEEE double.
     std::vector<uint64_t> special;
-    nps_row_desc *d_special = nullptr;
-    nps_row_desc *d_mx_desc = nullptr;
+    DevBuf<nps_row_desc> d_special;
+    DevBuf<nps_row_desc> d_mx_desc;
+
+    ~nps_scoredef() { (void)hipSetDevice(device); }
 };
+
+// n row descriptors of the host, on the device
+static hipError_t upload_desc(DevBuf<nps_row_desc> &d, const nps_row_desc *rows, uint64_t n) {
+    const hipError_t e = d.alloc(n);
+    return e != hipSuccess ? e : hipMemcpy(d.get(), rows, sizeof(nps_row_desc) * n, hipMemcpyHostToDevice);
+}
 constexpr int kMxBandBits = 30, kMxMaxBands = 8;
 
 // A PRESENT row the fixed-point kernels of NPS_FMT_GT2X cohorts cannot carry: a non-finite beta (0 x inf is NaN, every
@@ -1572,7 +1454,8 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
     if (n_desc && !rows) return fail(NPS_E_INVAL, "rows is NULL");
     int rc = select_device(device);
     if (rc) return rc;
-    nps_scoredef *d = new (std::nothrow) nps_scoredef;
+    std::unique_ptr<nps_scoredef> owner(new (std::nothrow) nps_scoredef);
+    nps_scoredef *d = owner.get();
     if (!d) return fail(NPS_E_NOMEM, "out of host memory");
     d->device = device;
     d->n_desc = n_desc;
@@ -1594,20 +1477,14 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
             d->data_index[j] = -1;
             d->host_rows.push_back(r);
         } else {
-            delete d;
             return fail(NPS_E_INVAL, "row %llu: bad kind %d", (unsigned long long)j, r.kind);
         }
     }
     d->m = data.size();
-    if (d->m > 0xfffffff0ull) {
-        delete d;
-        return fail(NPS_E_UNSUPPORTED, "too many rows");
-    }
+    if (d->m > 0xfffffff0ull) return fail(NPS_E_UNSUPPORTED, "too many rows");
     if (d->m) {
-        hipError_t e = hipMalloc(&d->d_desc, sizeof(nps_row_desc) * d->m);
-        if (e == hipSuccess)
-            e = hipMemcpy(d->d_desc, data.data(), sizeof(nps_row_desc) * d->m, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !d->special.empty()) {
+        HIP_TRY(upload_desc(d->d_desc, data.data(), d->m));
+        if (!d->special.empty()) {
             const uint64_t k = d->special.size();
             std::vector<nps_row_desc> sp(k);
             for (uint64_t i = 0; i < k; ++i) {
@@ -1615,17 +1492,14 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
                 data[d->special[i]].beta = 0.0;  // (from here on `data` is the fixed-point copy)
                 data[d->special[i]].eaf = 0.0;
             }
-            e = hipMalloc(&d->d_special, sizeof(nps_row_desc) * k);
-            if (e == hipSuccess) e = hipMemcpy(d->d_special, sp.data(), sizeof(nps_row_desc) * k, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMalloc(&d->d_mx_desc, sizeof(nps_row_desc) * d->m);
-            if (e == hipSuccess)
-                e = hipMemcpy(d->d_mx_desc, data.data(), sizeof(nps_row_desc) * d->m, hipMemcpyHostToDevice);
+            HIP_TRY(upload_desc(d->d_special, sp.data(), k));
+            HIP_TRY(upload_desc(d->d_mx_desc, data.data(), d->m));
         }
         // magnitude bands for the fixed-point kernel (north star: 1e-6 RELATIVE for every sample, also one whose only
         // rows are the definition's smallest): band b holds the rows with bound 2^-30(b+1) < v <= bound 2^-30b
         std::vector<int> band(d->m, 0);
         int n_bands = 1;
-        if (e == hipSuccess && d->mx_bound > 0.0) {
+        if (d->mx_bound > 0.0) {
             for (uint64_t j = 0; j < d->m; ++j) {
                 const nps_row_desc &r = data[j];
                 if (!std::isfinite(r.beta) || r.beta == 0.0) continue;
@@ -1637,9 +1511,9 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
                 n_bands = std::max(n_bands, band[j] + 1);
             }
         }
-        if (e == hipSuccess && n_bands > 1) {
+        if (n_bands > 1) {
             std::vector<nps_row_desc> copy(d->m);
-            for (int b = 0; b < n_bands && e == hipSuccess; ++b) {
+            for (int b = 0; b < n_bands; ++b) {
                 nps_scoredef::MxBand mb;
                 bool any = b == 0;
                 for (uint64_t j = 0; j < d->m; ++j) {
@@ -1652,37 +1526,18 @@ extern "C" int nps_scoredef_create(nps_scoredef **out, int device, const nps_row
                     }
                 }
                 if (!any) continue;  // an empty band costs no pass
-                e = hipMalloc(&mb.d_desc, sizeof(nps_row_desc) * d->m);
-                if (e == hipSuccess)
-                    e = hipMemcpy(mb.d_desc, copy.data(), sizeof(nps_row_desc) * d->m, hipMemcpyHostToDevice);
-                d->mx_bands.push_back(mb);
+                HIP_TRY(upload_desc(mb.d_desc, copy.data(), d->m));
+                d->mx_bands.push_back(std::move(mb));
             }
         }
-        if (e != hipSuccess) {
-            (void)hipFree(d->d_desc);
-            (void)hipFree(d->d_special);
-            (void)hipFree(d->d_mx_desc);
-            for (auto &mb : d->mx_bands) (void)hipFree(mb.d_desc);
-            delete d;
-            return fail(e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP,
-                        "uploading the score definition failed: %s", hipGetErrorString(e));
-        }
     }
-    *out = d;
+    *out = owner.release();
     return NPS_OK;
 }
 
 extern "C" uint64_t nps_scoredef_n_present(const nps_scoredef *d) { return d ? d->m : 0; }
 
-extern "C" void nps_scoredef_destroy(nps_scoredef *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipFree(d->d_desc);
-    (void)hipFree(d->d_special);
-    (void)hipFree(d->d_mx_desc);
-    for (auto &mb : d->mx_bands) (void)hipFree(mb.d_desc);
-    delete d;
-}
+extern "C" void nps_scoredef_destroy(nps_scoredef *d) { delete d; }
 
 // ------------------------------------------------------------------------------------------
 // resident scoring.  Two-pass mode: per block of rows, tally -> params -> accumulate.
@@ -1705,9 +1560,9 @@ static int materialize_resident_stats(nps_ctx *c) {
     if (!c->res_pending) return NPS_OK;
     std::vector<nps_locus_stat> dev(c->res_m);
     if (c->res_m) {
-        HIP_TRY(hipMemcpyAsync(dev.data(), c->d_rstats, sizeof(nps_locus_stat) * c->res_m,
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpyAsync(dev.data(), c->d_rstats.get(), sizeof(nps_locus_stat) * c->res_m,
+                               hipMemcpyDeviceToHost, c->stream.get()));
+        HIP_TRY(hipStreamSynchronize(c->stream.get()));
     }
     size_t h = 0;
     for (size_t j = 0; j < c->res_index.size(); ++j) {
@@ -1723,7 +1578,6 @@ static int materialize_resident_stats(nps_ctx *c) {
     return NPS_OK;
 }
 
-// (re)allocation helper: *p holds at least `need` elements of `elem` bytes afterwards
 // the reference's test `nmissing / N > --maxmis` (double division, nimpress.nim:565) is monotone in nmissing: the largest
 // count that is NOT over the rate (-1: none), found with that very expression -- the kernels compare integers
 static int64_t maxmis_threshold(uint64_t n, double rate) {
@@ -1739,35 +1593,6 @@ static int64_t maxmis_threshold(uint64_t n, double rate) {
     return (int64_t)lo;
 }
 
-static int grow(nps_ctx *c, void **p, uint64_t *cap, uint64_t need, size_t elem) {
-    if (need <= *cap) return NPS_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(p, elem * need));
-    *cap = need;
-    return NPS_OK;
-}
-
-static int ensure_resident_buffers(nps_ctx *c, uint64_t m_pad) {
-    if (m_pad <= c->res_cap) return NPS_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_rtally);
-    (void)hipFree(c->d_rlut);
-    (void)hipFree(c->d_rstats);
-    c->d_rtally = nullptr;
-    c->d_rlut = nullptr;
-    c->d_rstats = nullptr;
-    c->res_cap = 0;
-    c->rtally_clean = false;
-    HIP_TRY(hipMalloc(&c->d_rtally, sizeof(unsigned long long) * m_pad));
-    HIP_TRY(hipMalloc(&c->d_rlut, sizeof(double) * 4 * m_pad));
-    HIP_TRY(hipMalloc(&c->d_rstats, sizeof(nps_locus_stat) * m_pad));
-    c->res_cap = m_pad;
-    return NPS_OK;
-}
-
 // NPS_FMT_GT2X runs of a definition with special rows (mx_special): the fixed-point pass scored them at beta = eaf = 0 --
 // their tallies, statistics and decisions included, a product 0 x 0 is 0, and where it is NaN (an imputed NaN dosage) the
 // reference's product is NaN for any beta too.  Here the same rows come out of the strip layout into the row layout, a
@@ -1781,11 +1606,11 @@ static uint64_t mx_special_batch(const nps_ctx *c, uint64_t k) {
 
 static int mx_special_buffers(nps_ctx *c, const nps_scoredef *def) {
     const uint64_t B = mx_special_batch(c, def->special.size());
-    int rc = grow(c, (void **)&c->d_sp_plain, &c->sp_plain_cap, B * c->n_words, 4);
-    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_group, &c->sp_group_cap, B * c->stride_words, 4);
-    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_tally, &c->sp_tally_cap, B, sizeof(unsigned long long));
-    if (rc == NPS_OK) rc = grow(c, (void **)&c->d_sp_lut, &c->sp_lut_cap, 4 * B, sizeof(double));
-    return rc;
+    HIP_TRY(c->d_sp_plain.ensure(B * c->n_words, c->stream.get()));
+    HIP_TRY(c->d_sp_group.ensure(B * c->stride_words, c->stream.get()));
+    HIP_TRY(c->d_sp_tally.ensure(B, c->stream.get()));
+    HIP_TRY(c->d_sp_lut.ensure(4 * B, c->stream.get()));
+    return NPS_OK;
 }
 
 static int mx_special_pass(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
@@ -1799,18 +1624,18 @@ static int mx_special_pass(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row
         for (uint64_t j = b0; j < b0 + k;) {  // one launch per run of consecutive rows
             uint64_t e = j + 1;
             while (e < b0 + k && def->special[e] == def->special[e - 1] + 1) ++e;
-            HIP_TRY(launch_gt2x_to_rows(c->stream, co->d_data, c->n, co->n_rows, cohort_row0 + def->special[j], e - j,
-                                        c->d_sp_plain + (j - b0) * c->n_words, c->n_words));
+            HIP_TRY(launch_gt2x_to_rows(c->stream.get(), co->d_data.get(), c->n, co->n_rows, cohort_row0 + def->special[j], e - j,
+                                        c->d_sp_plain.get() + (j - b0) * c->n_words, c->n_words));
             j = e;
         }
-        HIP_TRY(launch_interleave_rows(c->stream, c->d_sp_plain, c->n_words, k, c->n, nullptr, c->d_sp_group,
+        HIP_TRY(launch_interleave_rows(c->stream.get(), c->d_sp_plain.get(), c->n_words, k, c->n, nullptr, c->d_sp_group.get(),
                                        c->stride_words));
-        HIP_TRY(launch_tally_packed(c->stream, c->d_sp_group, c->stride_words, c->n, k, c->d_sp_tally));
-        HIP_TRY(launch_row_params(c->stream, c->d_sp_tally, def->d_special + b0, k, k_pad, c->n, dev_params(c->params),
-                                  c->d_sp_lut, nullptr, scratch_nloci));
+        HIP_TRY(launch_tally_packed(c->stream.get(), c->d_sp_group.get(), c->stride_words, c->n, k, c->d_sp_tally.get()));
+        HIP_TRY(launch_row_params(c->stream.get(), c->d_sp_tally.get(), def->d_special.get() + b0, k, k_pad, c->n, dev_params(c->params),
+                                  c->d_sp_lut.get(), nullptr, scratch_nloci));
         AccumGeom g = c->geom;
         g.groups_per_chunk = std::max<uint32_t>(1, (uint32_t)((k_pad / 4 + g.n_chunks - 1) / g.n_chunks));
-        HIP_TRY(launch_accumulate(c->stream, c->d_sp_group, c->stride_words, k, c->d_sp_lut, g, c->d_part));
+        HIP_TRY(launch_accumulate(c->stream.get(), c->d_sp_group.get(), c->stride_words, k, c->d_sp_lut.get(), g, c->d_part.get()));
     }
     return NPS_OK;
 }
@@ -1826,15 +1651,15 @@ struct RunGuard {
 // the fused kernels' tally words must be zero on entry; their epilogue (fold_kernel) leaves them so
 static int tally_ready(nps_ctx *c) {
     if (!c->rtally_clean)
-        HIP_TRY(hipMemsetAsync(c->d_rtally, 0, sizeof(unsigned long long) * c->res_cap, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_rtally.get(), 0, sizeof(unsigned long long) * c->d_rtally.cap(), c->stream.get()));
     c->rtally_clean = false;
     return NPS_OK;
 }
 
 static int fused_epilogue(nps_ctx *c, const FusedPlan &plan, uint64_t n_tally) {
     ProfScope ps(c, P_REDUCE);
-    HIP_TRY(launch_fold(c->stream, c->d_part_fused, plan.Q, plan.part_team_stride, c->n, c->d_part,
-                        c->chunks_used == 0 ? 1 : 0, c->d_rtally, n_tally, c->d_timeout, c->d_nloci + 1));
+    HIP_TRY(launch_fold(c->stream.get(), c->d_part_fused.get(), plan.Q, plan.part_team_stride, c->n, c->d_part.get(),
+                        c->chunks_used == 0 ? 1 : 0, c->d_rtally.get(), n_tally, c->d_timeout.get(), c->d_nloci.get() + 1));
     c->chunks_used = std::max(c->chunks_used, 1u);
     c->rtally_clean = true;  // all words were zero before the run, [0, m_pad) are zero again
     return NPS_OK;
@@ -1869,13 +1694,10 @@ static int single_read(nps_ctx *c, RunGuard &guard, const FusedPlan &plan, uint6
 // buffers of a strip run (a failed allocation leaves the context usable: nothing has been queued yet)
 static int mx_run_buffers(nps_ctx *c, const nps_cohort *co, const nps_scoredef *def, uint64_t m_pad, MxRouted *mx) {
     const MxPlan &mxp = mx->plan;
-    int rc = grow(c, (void **)&c->d_mx_cpart, &c->mx_cpart_cap, mxp.cpart_floats, sizeof(float));
-    if (rc) return rc;
-    if (8 + 2ull * mxp.Q > c->mx_const_cap) {
-        rc = grow(c, (void **)&c->d_mx_const, &c->mx_const_cap, 8 + 2ull * mxp.Q, sizeof(double));
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_mx_const, 0, sizeof(double) * c->mx_const_cap, c->stream));
-    }
+    bool grew = false;
+    HIP_TRY(c->d_mx_cpart.ensure(mxp.cpart_floats, c->stream.get()));
+    HIP_TRY(c->d_mx_const.ensure(8 + 2ull * mxp.Q, c->stream.get(), &grew));
+    if (grew) HIP_TRY(hipMemsetAsync(c->d_mx_const.get(), 0, sizeof(double) * c->d_mx_const.cap(), c->stream.get()));
     if (mx->route == MxRoute::InPassKeep) {  // (the cohort's kept tallies: allocated once, by whoever keeps them first)
         nps_cohort *mco = const_cast<nps_cohort *>(co);
         std::lock_guard<std::mutex> lk(mco->tally_mutex);
@@ -1885,20 +1707,17 @@ static int mx_run_buffers(nps_ctx *c, const nps_cohort *co, const nps_scoredef *
         }
     }
     if (!def->special.empty()) {
-        rc = mx_special_buffers(c, def);
+        int rc = mx_special_buffers(c, def);
         if (rc) return rc;
     }
     if (mxp.given) {
-        rc = grow(c, (void **)&c->d_mx_ops, &c->mx_ops_cap, m_pad, 48);
-        if (rc == NPS_OK) rc = grow(c, (void **)&c->d_mx_cblk, &c->mx_cblk_cap, m_pad / 128, sizeof(double));
-        if (rc) return rc;
+        HIP_TRY(c->d_mx_ops.ensure(m_pad, c->stream.get()));
+        HIP_TRY(c->d_mx_cblk.ensure(m_pad / 128, c->stream.get()));
     }
-    const uint64_t need1 = (uint64_t)((mxp.P + 15) / 16) * m_pad;
-    if (need1 > c->mx_tally1_cap) {
-        rc = grow(c, (void **)&c->d_mx_tally1, &c->mx_tally1_cap, need1, sizeof(unsigned long long));
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_mx_tally1, 0, sizeof(unsigned long long) * c->mx_tally1_cap, c->stream));
-    }
+    grew = false;
+    HIP_TRY(c->d_mx_tally1.ensure((uint64_t)((mxp.P + 15) / 16) * m_pad, c->stream.get(), &grew));
+    if (grew)
+        HIP_TRY(hipMemsetAsync(c->d_mx_tally1.get(), 0, sizeof(unsigned long long) * c->d_mx_tally1.cap(), c->stream.get()));
     return NPS_OK;
 }
 
@@ -1908,31 +1727,31 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
     const MxPlan &mxp = mx.plan;
     const MxRoute route = mx.route;
     const size_t n_bands = std::max<size_t>(1, def->mx_bands.size());  // (no bands: the definition is its one band)
-    unsigned long long *scratch_nloci = reinterpret_cast<unsigned long long *>(c->d_mx_const);  // (the 8 scratch doubles)
+    unsigned long long *scratch_nloci = reinterpret_cast<unsigned long long *>(c->d_mx_const.get());  // (the 8 scratch doubles)
     MxRun r;
-    r.d_units = co->d_data;
+    r.d_units = co->d_data.get();
     r.n_sb_cohort = gt2x_superblocks(co->n_rows);
     r.sb0 = cohort_row0 >> 7;
     r.n_samples = c->n;
     r.n_rows = def->m;
     r.prm = dev_params(c->params);
     r.t_maxmis = maxmis_threshold(c->n, c->params.max_missing_rate);
-    r.d_tally = c->d_rtally;
-    r.d_const_sum = c->d_mx_const + 8;
-    r.d_cpart = c->d_mx_cpart;
-    r.d_timeout = c->d_timeout;
-    r.d_pre = c->d_rlut;
-    r.d_tally1 = c->d_mx_tally1;
-    r.d_tally_given = route == MxRoute::GivenKept ? co->d_mx_row_tally + cohort_row0 : c->d_rtally;
-    r.d_ops = c->d_mx_ops;
-    r.d_const_part = c->d_mx_cblk;
-    r.d_done = c->d_timeout + 17;
-    r.d_part0 = c->d_part;
-    r.d_status = c->d_nloci + 1;
+    r.d_tally = c->d_rtally.get();
+    r.d_const_sum = c->d_mx_const.get() + 8;
+    r.d_cpart = c->d_mx_cpart.get();
+    r.d_timeout = c->d_timeout.get();
+    r.d_pre = c->d_rlut.get();
+    r.d_tally1 = c->d_mx_tally1.get();
+    r.d_tally_given = route == MxRoute::GivenKept ? co->d_mx_row_tally.get() + cohort_row0 : c->d_rtally.get();
+    r.d_ops = c->d_mx_ops.get();
+    r.d_const_part = c->d_mx_cblk.get();
+    r.d_done = c->d_timeout.get() + 17;
+    r.d_part0 = c->d_part.get();
+    r.d_status = c->d_nloci.get() + 1;
     for (size_t b = 0; b < n_bands; ++b) {  // band 0 counts nloci and writes the statistics
         const bool banded = !def->mx_bands.empty();
         const double bound = banded ? def->mx_bands[b].bound : def->mx_bound;
-        r.d_desc = banded ? def->mx_bands[b].d_desc : def->d_mx_desc ? def->d_mx_desc : def->d_desc;
+        r.d_desc = banded ? def->mx_bands[b].d_desc.get() : def->d_mx_desc.get() ? def->d_mx_desc.get() : def->d_desc.get();
         // fixed-point scale: every weight of the band below 2^56 (fourteen hexadecimal digits)
         r.F = 56;
         if (bound > 0.0) {
@@ -1940,22 +1759,22 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
             (void)std::frexp(bound, &e2);  // bound < 2^e2
             r.F = std::min(1000, std::max(-1000, 56 - e2));
         }
-        r.d_stats = b == 0 ? c->d_rstats : nullptr;
-        r.d_nloci = b == 0 ? c->d_nloci : scratch_nloci;
+        r.d_stats = b == 0 ? c->d_rstats.get() : nullptr;
+        r.d_nloci = b == 0 ? c->d_nloci.get() : scratch_nloci;
         r.overwrite = c->chunks_used == 0 ? 1 : 0;
         const bool keep = route == MxRoute::InPassKeep && b == 0;
-        r.d_keep = keep ? co->d_mx_row_tally : nullptr;
+        r.d_keep = keep ? co->d_mx_row_tally.get() : nullptr;
         r.n_keep = keep ? (uint64_t)mxp.n_sb * 128 : 0;
         int rc = tally_ready(c);
         if (rc) return rc;
         if (route == MxRoute::GivenTallied) {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_mx_tally(c->stream, mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally));
+            HIP_TRY(launch_mx_tally(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally.get()));
         }
         hipError_t fe;
         {
             ProfScope ps(c, mxp.given ? P_ACCUM : P_FUSED);
-            fe = mxp.given ? launch_mx_given(c->stream, mxp, r) : launch_fused_mx(c->stream, mxp, r);
+            fe = mxp.given ? launch_mx_given(c->stream.get(), mxp, r) : launch_fused_mx(c->stream.get(), mxp, r);
         }
         if (fe != hipSuccess) {
             (void)hipGetLastError();  // the runtime refused the cooperative grid: nothing ran
@@ -1965,8 +1784,8 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         guard.armed = true;
         {
             ProfScope ps(c, P_REDUCE);
-            HIP_TRY(launch_mx_fold(c->stream, mxp, r));
-            HIP_TRY(hipMemsetAsync(r.d_const_sum, 0, sizeof(double) * 2 * mxp.Q, c->stream));
+            HIP_TRY(launch_mx_fold(c->stream.get(), mxp, r));
+            HIP_TRY(hipMemsetAsync(r.d_const_sum, 0, sizeof(double) * 2 * mxp.Q, c->stream.get()));
         }
         c->chunks_used = std::max(c->chunks_used, 1u);
         c->rtally_clean = true;
@@ -1980,7 +1799,7 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         // from another thread and stream): one wait, on the cohort's first pass only
         // (a superblock that was valid before -- rows uploaded, then others rewritten by the generator -- has received the
         //  same words again: a reader on another thread sees complete words at every moment)
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream.get()));
         nps_cohort *mco = const_cast<nps_cohort *>(co);
         std::lock_guard<std::mutex> lk(mco->tally_mutex);
         mx_tallies_mark(mco, 0, gt2x_superblocks(co->n_rows), true);
@@ -1995,13 +1814,13 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
     const uint64_t m = def->m;
     const bool is_ds16 = co->format == NPS_FMT_DS16;
     const uint64_t stride_f = co->stride_bytes / 4;  // (NPS_FMT_DS32 only below the fused branch)
-    const float *ds = (const float *)((const char *)co->d_data + cohort_row0 * co->stride_bytes);
+    const float *ds = (const float *)((const char *)co->d_data.get() + cohort_row0 * co->stride_bytes);
     if (plan.ok && c->n) {
         bool ran = false;
         int rc = single_read(c, guard, plan, n_tally, "fused DS", mode == NPS_MODE_AUTO && !is_ds16, [&]() {
-            return launch_ds_fused(c->stream, plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc,
-                                   dev_params(c->params), maxmis_threshold(c->n, c->params.max_missing_rate), c->d_rtally,
-                                   c->d_rstats, c->d_nloci, c->d_part_fused, c->d_timeout);
+            return launch_ds_fused(c->stream.get(), plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc.get(),
+                                   dev_params(c->params), maxmis_threshold(c->n, c->params.max_missing_rate), c->d_rtally.get(),
+                                   c->d_rstats.get(), c->d_nloci.get(), c->d_part_fused.get(), c->d_timeout.get());
         }, &ran);
         if (rc || ran) return rc;
     }
@@ -2017,19 +1836,19 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         const uint64_t k = std::min(block_rows, m - r0);
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_ds_tally(c->stream, ds + r0 * stride_f, stride_f, c->n, def->d_desc + r0,
-                                    k, c->d_rds_tally + r0));
+            HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0,
+                                    k, c->d_rds_tally.get() + r0));
         }
         {
             ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_ds_params(c->stream, c->d_rds_tally + r0, def->d_desc + r0, k, c->n,
-                                     dev_params(c->params), c->d_rds_rowp + r0, c->d_rstats + r0,
-                                     c->d_nloci));
+            HIP_TRY(launch_ds_params(c->stream.get(), c->d_rds_tally.get() + r0, def->d_desc.get() + r0, k, c->n,
+                                     dev_params(c->params), c->d_rds_rowp.get() + r0, c->d_rstats.get() + r0,
+                                     c->d_nloci.get()));
         }
         {
             ProfScope ps(c, P_ACCUM);
-            HIP_TRY(launch_ds_accumulate(c->stream, ds + r0 * stride_f, stride_f, c->n,
-                                         c->d_rds_rowp + r0, k, c->d_part, c->n_chunks,
+            HIP_TRY(launch_ds_accumulate(c->stream.get(), ds + r0 * stride_f, stride_f, c->n,
+                                         c->d_rds_rowp.get() + r0, k, c->d_part.get(), c->n_chunks,
                                          c->geom.part_chunk_stride));
         }
     }
@@ -2041,21 +1860,21 @@ static int score_run_gt2(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint
                          int mode, const FusedPlan &plan, uint64_t n_tally) {
     const uint64_t m = def->m;
     const uint64_t stride_words = co->stride_bytes / 4;
-    const uint32_t *codes = (const uint32_t *)co->d_data + (cohort_row0 >> 2) * stride_words * 4;
-    const nps_row_desc *d_desc = def->d_desc;
+    const uint32_t *codes = (const uint32_t *)co->d_data.get() + (cohort_row0 >> 2) * stride_words * 4;
+    const nps_row_desc *d_desc = def->d_desc.get();
     const int parity = co->optimized ? 1 : 0;  // the kernels undo the parity layout for the tally
     if (plan.ok && c->n) {
         bool ran = false;
         int rc = single_read(c, guard, plan, n_tally, "fused", mode == NPS_MODE_AUTO, [&]() {
-            return launch_fused(c->stream, plan, codes, stride_words, c->n, m, d_desc, dev_params(c->params), c->d_rtally,
-                                c->d_rstats, c->d_nloci, c->d_part_fused, c->d_timeout, parity);
+            return launch_fused(c->stream.get(), plan, codes, stride_words, c->n, m, d_desc, dev_params(c->params), c->d_rtally.get(),
+                                c->d_rstats.get(), c->d_nloci.get(), c->d_part_fused.get(), c->d_timeout.get(), parity);
         }, &ran);
 #ifdef NPS_DIAGNOSTICS
         if (rc == NPS_OK && ran && getenv("NPS_TELEMETRY")) {  // diagnostics of the control wave (cycles, summed)
             unsigned long long t[8] = {0};
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipMemcpy(t, (char *)c->d_timeout + 16, sizeof t, hipMemcpyDeviceToHost);
-            (void)hipMemset((char *)c->d_timeout + 16, 0, sizeof t);
+            (void)hipStreamSynchronize(c->stream.get());
+            (void)hipMemcpy(t, (char *)c->d_timeout.get() + 16, sizeof t, hipMemcpyDeviceToHost);
+            (void)hipMemset((char *)c->d_timeout.get() + 16, 0, sizeof t);
             const double wg = (double)plan.P * plan.Q, st = t[4] ? (double)t[4] : 1.0;
             fprintf(stderr, "[nps] fused P=%u Q=%u T=%u: per step per WG: spins %.2f, poll wait "
                     "%.0f cyc, control chain %.0f cyc, barrier wait %.0f cyc (steps/WG %.0f)\n",
@@ -2078,22 +1897,22 @@ static int score_run_gt2(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint
         const uint64_t k_pad = (k + 3) / 4 * 4;  // only the last block can be ragged
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_packed(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words,
-                                        c->n, k, c->d_rtally + r0, parity));
+            HIP_TRY(launch_tally_packed(c->stream.get(), codes + (r0 >> 2) * stride_words * 4, stride_words,
+                                        c->n, k, c->d_rtally.get() + r0, parity));
         }
         {
             ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_row_params(c->stream, c->d_rtally + r0, d_desc + r0, k, k_pad, c->n,
-                                      dev_params(c->params), c->d_rlut + r0 * 4, c->d_rstats + r0,
-                                      c->d_nloci));
+            HIP_TRY(launch_row_params(c->stream.get(), c->d_rtally.get() + r0, d_desc + r0, k, k_pad, c->n,
+                                      dev_params(c->params), c->d_rlut.get() + r0 * 4, c->d_rstats.get() + r0,
+                                      c->d_nloci.get()));
         }
         if (c->n) {
             AccumGeom g = c->geom;
             const uint32_t groups = (uint32_t)(k_pad / 4);
             g.groups_per_chunk = std::max(1u, (groups + g.n_chunks - 1) / g.n_chunks);
             ProfScope ps(c, P_ACCUM);
-            HIP_TRY(launch_accumulate(c->stream, codes + (r0 >> 2) * stride_words * 4, stride_words, k,
-                                      c->d_rlut + r0 * 4, g, c->d_part, parity));
+            HIP_TRY(launch_accumulate(c->stream.get(), codes + (r0 >> 2) * stride_words * 4, stride_words, k,
+                                      c->d_rlut.get() + r0 * 4, g, c->d_part.get(), parity));
         }
     }
     return NPS_OK;
@@ -2229,23 +2048,20 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
     const bool fused = plan.ok && c->n;
     // (the single-read DS kernel keeps a PAIR of tally words per row)
     const uint64_t n_tally = is_ds && fused ? 2 * m_pad : m_pad;
-    rc = ensure_resident_buffers(c, n_tally);
-    if (rc) return rc;
+    bool grew = false;
+    const hipError_t ge = c->d_rtally.ensure(n_tally, c->stream.get(), &grew);
+    if (grew) c->rtally_clean = false;  // (also where the allocation then failed: the old words are gone)
+    HIP_TRY(ge);
+    HIP_TRY(c->d_rlut.ensure(4 * n_tally, c->stream.get()));
+    HIP_TRY(c->d_rstats.ensure(n_tally, c->stream.get()));
     if (is_mx && c->n) {
         rc = mx_run_buffers(c, co, def, m_pad, &mx);
         if (rc) return rc;
     }
-    if (fused) {
-        rc = grow(c, (void **)&c->d_part_fused, &c->part_fused_cap,
-                  (uint64_t)plan.Q * plan.part_team_stride, sizeof(double));
-        if (rc) return rc;
-    }
-    if (is_ds && m_pad > c->res_ds_cap) {
-        uint64_t cap_a = c->res_ds_cap, cap_b = c->res_ds_cap;
-        rc = grow(c, (void **)&c->d_rds_tally, &cap_a, m_pad, sizeof(DsTally));
-        if (rc == NPS_OK) rc = grow(c, (void **)&c->d_rds_rowp, &cap_b, m_pad, sizeof(DsRowP));
-        c->res_ds_cap = std::min(cap_a, cap_b);
-        if (rc) return rc;
+    if (fused) HIP_TRY(c->d_part_fused.ensure((uint64_t)plan.Q * plan.part_team_stride, c->stream.get()));
+    if (is_ds) {
+        HIP_TRY(c->d_rds_tally.ensure(m_pad, c->stream.get()));
+        HIP_TRY(c->d_rds_rowp.ensure(m_pad, c->stream.get()));
     }
 
     // ---- launches
@@ -2271,7 +2087,7 @@ extern "C" int nps_score_cohort(nps_ctx *c, const nps_cohort *co, uint64_t cohor
     rc = nps_score_cohort_def(c, co, cohort_row0, def, mode);
     // the launches read def->d_desc: complete them before the temporary definition goes away
     if (rc == NPS_OK) {
-        hipError_t e = hipStreamSynchronize(c->stream);
+        hipError_t e = hipStreamSynchronize(c->stream.get());
         if (e != hipSuccess) rc = fail(NPS_E_HIP, "resident scoring failed: %s", hipGetErrorString(e));
     }
     nps_scoredef_destroy(def);
@@ -2298,16 +2114,16 @@ extern "C" int nps_cohort_convert(nps_cohort *dst, const nps_cohort *src) {
         std::lock_guard<std::mutex> lk(dst->tally_mutex);
         const uint64_t n_sb = gt2x_superblocks(dst->n_rows);
         HIP_TRY(mx_tallies_alloc(dst));
-        HIP_TRY(hipMemsetAsync(dst->d_mx_row_tally, 0, sizeof(unsigned long long) * n_sb * 128, nullptr));
-        HIP_TRY(launch_fill_gt2x_from_gt2(nullptr, (const uint32_t *)src->d_data, src->stride_bytes / 4, src->n_samples,
-                                          src->n_rows, dst->d_data, dst->d_mx_row_tally));
+        HIP_TRY(hipMemsetAsync(dst->d_mx_row_tally.get(), 0, sizeof(unsigned long long) * n_sb * 128, nullptr));
+        HIP_TRY(launch_fill_gt2x_from_gt2(nullptr, (const uint32_t *)src->d_data.get(), src->stride_bytes / 4, src->n_samples,
+                                          src->n_rows, dst->d_data.get(), dst->d_mx_row_tally.get()));
         HIP_TRY(hipDeviceSynchronize());
         mx_tallies_mark(dst, 0, n_sb, true);
         return NPS_OK;
     }
     // units and, from the same tiles, the whole-row tallies (tallyAlleles nimpress.nim:32-47)
-    HIP_TRY(launch_convert_gt2m(nullptr, (const uint32_t *)src->d_data, src->stride_bytes / 4, src->n_samples,
-                                src->n_rows, dst->d_data, dst->d_row_tally));
+    HIP_TRY(launch_convert_gt2m(nullptr, (const uint32_t *)src->d_data.get(), src->stride_bytes / 4, src->n_samples,
+                                src->n_rows, dst->d_data.get(), dst->d_row_tally.get()));
     HIP_TRY(hipDeviceSynchronize());
     return NPS_OK;
 }
@@ -2324,7 +2140,7 @@ extern "C" int nps_cohort_row_tallies(const nps_cohort *c, uint64_t row0, uint64
     if (nrows == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<unsigned long long> t(nrows);
-    HIP_TRY(hipMemcpy(t.data(), (kept ? c->d_mx_row_tally : c->d_row_tally) + row0, sizeof(unsigned long long) * nrows,
+    HIP_TRY(hipMemcpy(t.data(), (kept ? c->d_mx_row_tally.get() : c->d_row_tally.get()) + row0, sizeof(unsigned long long) * nrows,
                       hipMemcpyDeviceToHost));
     for (uint64_t j = 0; j < nrows; ++j) {
         if (nmissing_out) nmissing_out[j] = kept ? (t[j] >> 28) & 0xfffffffull : t[j] >> 32;
@@ -2360,9 +2176,9 @@ static int mx_keep_tallies_locked(nps_cohort *c) {
                 }
                 uint64_t e = sb + 1;
                 while (e < n_sb && !mx_tallies_valid(c, e, 1)) ++e;
-                HIP_TRY(hipMemsetAsync(c->d_mx_row_tally + sb * 128, 0, sizeof(unsigned long long) * (e - sb) * 128, nullptr));
+                HIP_TRY(hipMemsetAsync(c->d_mx_row_tally.get() + sb * 128, 0, sizeof(unsigned long long) * (e - sb) * 128, nullptr));
                 mp.n_sb = (uint32_t)(e - sb);
-                HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data, n_sb, sb, c->n_samples, c->d_mx_row_tally + sb * 128));
+                HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data.get(), n_sb, sb, c->n_samples, c->d_mx_row_tally.get() + sb * 128));
                 sb = e;
             }
             HIP_TRY(hipDeviceSynchronize());
@@ -2403,9 +2219,14 @@ struct nps_multidef {
     int device = 0;
     int S = 0;
     uint64_t n_desc = 0;
-    nps_row_desc *d_desc = nullptr;  // [S][n_desc]
-    int *d_F = nullptr;              // fixed-point exponent per score: weight * 2^F is an integer below 2^(8 ND - 9)
+    DevBuf<nps_row_desc> d_desc;     // [S][n_desc]
+    DevBuf<int> d_F;                 // fixed-point exponent per score: weight * 2^F is an integer below 2^(8 ND - 9)
     int ND = 7;                      // base-256 digits per weight
+
+    ~nps_multidef() {  // a pass that reads the definitions may still be queued
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
 };
 
 extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const nps_row_desc *rows, int n_scores,
@@ -2456,27 +2277,17 @@ extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const np
     }
     int rc = select_device(device);
     if (rc) return rc;
-    nps_multidef *d = new (std::nothrow) nps_multidef;
+    std::unique_ptr<nps_multidef> owner(new (std::nothrow) nps_multidef);
+    nps_multidef *d = owner.get();
     if (!d) return fail(NPS_E_NOMEM, "out of host memory");
     d->device = device;
     d->S = n_scores;
     d->ND = ND;
     d->n_desc = n_desc;
-    hipError_t e = hipMalloc(&d->d_F, sizeof(int) * NPS_MULTI_MAX_SCORES);
-    if (e == hipSuccess) e = hipMemcpy(d->d_F, F, sizeof(int) * n_scores, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_desc) {
-        e = hipMalloc(&d->d_desc, sizeof(nps_row_desc) * n_desc * n_scores);
-        if (e == hipSuccess)
-            e = hipMemcpy(d->d_desc, rows, sizeof(nps_row_desc) * n_desc * n_scores, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        (void)hipFree(d->d_F);
-        (void)hipFree(d->d_desc);
-        delete d;
-        return fail(e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP, "uploading the score definitions failed: %s",
-                    hipGetErrorString(e));
-    }
-    *out = d;
+    HIP_TRY(d->d_F.alloc(NPS_MULTI_MAX_SCORES));
+    HIP_TRY(hipMemcpy(d->d_F.get(), F, sizeof(int) * n_scores, hipMemcpyHostToDevice));
+    if (n_desc) HIP_TRY(upload_desc(d->d_desc, rows, n_desc * n_scores));
+    *out = owner.release();
     return NPS_OK;
 }
 
@@ -2485,64 +2296,44 @@ extern "C" int nps_multidef_create(nps_multidef **out, int device, const nps_row
     return nps_multidef_create_bits(out, device, rows, n_scores, n_desc, 0);
 }
 
-extern "C" void nps_multidef_destroy(nps_multidef *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(d->d_desc);
-    (void)hipFree(d->d_F);
-    delete d;
-}
+extern "C" void nps_multidef_destroy(nps_multidef *d) { delete d; }
 
 struct nps_multi {
+    Stream stream;  // (first: destroyed last)
     int device = 0, S = 0, cus = 0;
-    hipStream_t stream = nullptr;
     uint64_t n = 0;
     nps_params params{};
-    void *d_state = nullptr;      // MultiState[S]
-    double *d_part = nullptr;     // [S][n] float64 running sums
+    DevBuf<unsigned char> d_state;  // MultiState[S]
+    DevBuf<double> d_part;          // [S][n] float64 running sums
     bool have_sums = false;
-    void *d_table = nullptr;
-    uint64_t table_cap = 0;
-    int32_t *d_partial = nullptr;
-    uint64_t partial_cap = 0;
-    double *d_offsets = nullptr, *d_scores = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<unsigned char> d_table;  // the weight table and its flags (bytes), grown on demand
+    DevBuf<int32_t> d_partial;      // grown on demand
+    DevBuf<double> d_offsets, d_scores;
+    Event ev[4];
     double ms[3] = {0.0, 0.0, 0.0};  // params, product, fold of all calls since the last reset
     bool timed = false;
     int coarse_missing = 0;          // nps_multi_set_missing_weight_bits: leading base-256 digits kept (4 = 32 bits, 5 = 40; 0 = all)
     bool broken = false;             // a HIP call failed between the first and the last launch of a pass
+
+    ~nps_multi() {  // queued work may still use what the members release
+        (void)hipSetDevice(device);
+        if (stream.get()) (void)hipStreamSynchronize(stream.get());
+    }
 };
 
 // add the device time of the last call (if its events have not been read yet) to the running totals
 static void multi_drain_timing(nps_multi *m) {
     if (!m->timed) return;
     float a = 0.f, b = 0.f, c = 0.f;
-    if (hipEventSynchronize(m->ev[3]) == hipSuccess) {
-        (void)hipEventElapsedTime(&a, m->ev[0], m->ev[1]);
-        (void)hipEventElapsedTime(&b, m->ev[1], m->ev[2]);
-        (void)hipEventElapsedTime(&c, m->ev[2], m->ev[3]);
+    if (hipEventSynchronize(m->ev[3].get()) == hipSuccess) {
+        (void)hipEventElapsedTime(&a, m->ev[0].get(), m->ev[1].get());
+        (void)hipEventElapsedTime(&b, m->ev[1].get(), m->ev[2].get());
+        (void)hipEventElapsedTime(&c, m->ev[2].get(), m->ev[3].get());
         m->ms[0] += a;
         m->ms[1] += b;
         m->ms[2] += c;
     }
     m->timed = false;
-}
-
-static void free_multi(nps_multi *m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    (void)hipFree(m->d_state);
-    (void)hipFree(m->d_part);
-    (void)hipFree(m->d_table);
-    (void)hipFree(m->d_partial);
-    (void)hipFree(m->d_offsets);
-    (void)hipFree(m->d_scores);
-    for (hipEvent_t e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
 }
 
 extern "C" int nps_multi_create(nps_multi **out, int device, uint64_t n_samples, const nps_params *params,
@@ -2556,32 +2347,29 @@ extern "C" int nps_multi_create(nps_multi **out, int device, uint64_t n_samples,
     if (n_samples > 0x7fffffffull) return fail(NPS_E_UNSUPPORTED, "n_samples too large");
     rc = select_device(device);
     if (rc) return rc;
-    nps_multi *m = new (std::nothrow) nps_multi;
+    std::unique_ptr<nps_multi> owner(new (std::nothrow) nps_multi);
+    nps_multi *m = owner.get();
     if (!m) return fail(NPS_E_NOMEM, "out of host memory");
     m->device = device;
     m->S = n_scores;
     m->n = n_samples;
     m->params = *params;
     hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    m->cus = e == hipSuccess ? prop.multiProcessorCount : 256;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    m->cus = prop.multiProcessorCount;
     const size_t sb = multi_state_bytes() * NPS_MULTI_MAX_SCORES;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&m->d_state, sb);
-    if (e == hipSuccess) e = hipMemset(m->d_state, 0, sb);
-    if (e == hipSuccess) e = hipMalloc(&m->d_part, sizeof(double) * std::max<uint64_t>(n_samples, 1) * n_scores);
-    if (e == hipSuccess) e = hipMalloc(&m->d_scores, sizeof(double) * std::max<uint64_t>(n_samples, 1) * n_scores);
-    if (e == hipSuccess) e = hipMalloc(&m->d_offsets, sizeof(double) * NPS_MULTI_MAX_SCORES);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&m->ev[k]);
-    if (e != hipSuccess) {
-        free_multi(m);
-        return fail(e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP, "nps_multi_create: %s", hipGetErrorString(e));
-    }
-    *out = m;
+    HIP_TRY(m->stream.create());
+    HIP_TRY(m->d_state.alloc(sb));
+    HIP_TRY(hipMemset(m->d_state.get(), 0, sb));
+    HIP_TRY(m->d_part.alloc(std::max<uint64_t>(n_samples, 1) * n_scores));
+    HIP_TRY(m->d_scores.alloc(std::max<uint64_t>(n_samples, 1) * n_scores));
+    HIP_TRY(m->d_offsets.alloc(NPS_MULTI_MAX_SCORES));
+    for (int k = 0; k < 4; ++k) HIP_TRY(m->ev[k].create(hipEventDefault));
+    *out = owner.release();
     return NPS_OK;
 }
 
-extern "C" void nps_multi_destroy(nps_multi *m) { free_multi(m); }
+extern "C" void nps_multi_destroy(nps_multi *m) { delete m; }
 
 extern "C" int nps_multi_set_missing_weight_bits(nps_multi *m, int bits) {
     if (!m) return fail(NPS_E_INVAL, "ctx is NULL");
@@ -2600,7 +2388,7 @@ extern "C" int nps_multi_reset(nps_multi *m, const nps_params *params) {
     }
     HIP_TRY(hipSetDevice(m->device));
     multi_drain_timing(m);
-    HIP_TRY(hipMemsetAsync(m->d_state, 0, multi_state_bytes() * NPS_MULTI_MAX_SCORES, m->stream));
+    HIP_TRY(hipMemsetAsync(m->d_state.get(), 0, multi_state_bytes() * NPS_MULTI_MAX_SCORES, m->stream.get()));
     m->broken = false;
     m->have_sums = false;
     m->ms[0] = m->ms[1] = m->ms[2] = 0.0;
@@ -2624,49 +2412,35 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
     if (def->n_desc == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(m->device));
     const MultiPlan pl = multi_plan(m->n, def->n_desc, m->S, def->ND, m->coarse_missing, m->cus);
-    if (pl.table_bytes() + pl.flag_bytes() > m->table_cap) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        (void)hipFree(m->d_table);
-        m->d_table = nullptr;
-        m->table_cap = 0;
-        HIP_TRY(hipMalloc(&m->d_table, pl.table_bytes() + pl.flag_bytes()));
-        m->table_cap = pl.table_bytes() + pl.flag_bytes();
-    }
-    if (pl.partial_elems() > m->partial_cap) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        (void)hipFree(m->d_partial);
-        m->d_partial = nullptr;
-        m->partial_cap = 0;
-        HIP_TRY(hipMalloc(&m->d_partial, sizeof(int32_t) * std::max<uint64_t>(pl.partial_elems(), 1)));
-        m->partial_cap = pl.partial_elems();
-    }
+    HIP_TRY(m->d_table.ensure(pl.table_bytes() + pl.flag_bytes(), m->stream.get()));
+    HIP_TRY(m->d_partial.ensure(pl.partial_elems(), m->stream.get()));
     // (the timing events are about to be re-recorded: read the previous pass's times only if it has completed already --
     //  a caller that queues pass after pass is never blocked here; its per-pass times are then not accumulated)
-    if (m->timed && hipEventQuery(m->ev[3]) == hipSuccess) multi_drain_timing(m);
+    if (m->timed && hipEventQuery(m->ev[3].get()) == hipSuccess) multi_drain_timing(m);
     m->timed = false;
     // Everything that can be refused has been checked and allocated.  From here a HIP failure leaves the running
     // sums and counts of the context undefined: it is marked broken (NPS_E_STATE until nps_multi_reset).
     // (multi_params_kernel writes every fragment of the table, zeros for unused columns and padding rows)
     auto run = [&]() -> hipError_t {
-        hipError_t e = hipEventRecord(m->ev[0], m->stream);
+        hipError_t e = hipEventRecord(m->ev[0].get(), m->stream.get());
         if (e != hipSuccess) return e;
-        e = launch_multi_params(m->stream, co->d_row_tally + cohort_row0, def->d_desc, def->n_desc, m->S, pl, m->n,
-                                dev_params(m->params), def->d_F, m->d_table, m->d_state, m->coarse_missing);
+        e = launch_multi_params(m->stream.get(), co->d_row_tally.get() + cohort_row0, def->d_desc.get(), def->n_desc, m->S, pl, m->n,
+                                dev_params(m->params), def->d_F.get(), m->d_table.get(), m->d_state.get(), m->coarse_missing);
         if (e != hipSuccess) return e;
-        e = hipEventRecord(m->ev[1], m->stream);
+        e = hipEventRecord(m->ev[1].get(), m->stream.get());
         if (e != hipSuccess) return e;
         if (m->n) {
-            e = launch_multi_mfma(m->stream, pl, co->d_data, cohort_row0 / 128, m->d_table, m->d_partial, m->d_state,
-                                  co->d_row_tally + cohort_row0, def->n_desc,
-                                  reinterpret_cast<uint32_t *>(static_cast<char *>(m->d_table) + pl.table_bytes()));
+            e = launch_multi_mfma(m->stream.get(), pl, co->d_data.get(), cohort_row0 / 128, m->d_table.get(), m->d_partial.get(), m->d_state.get(),
+                                  co->d_row_tally.get() + cohort_row0, def->n_desc,
+                                  reinterpret_cast<uint32_t *>(m->d_table.get() + pl.table_bytes()));
             if (e != hipSuccess) return e;
         }
-        e = hipEventRecord(m->ev[2], m->stream);
+        e = hipEventRecord(m->ev[2].get(), m->stream.get());
         if (e != hipSuccess) return e;
-        e = launch_multi_fold(m->stream, pl, m->d_partial, m->n, m->S, def->d_F, m->d_part, m->have_sums ? 0 : 1,
-                              m->d_state);
+        e = launch_multi_fold(m->stream.get(), pl, m->d_partial.get(), m->n, m->S, def->d_F.get(), m->d_part.get(), m->have_sums ? 0 : 1,
+                              m->d_state.get());
         if (e != hipSuccess) return e;
-        return hipEventRecord(m->ev[3], m->stream);
+        return hipEventRecord(m->ev[3].get(), m->stream.get());
     };
     const hipError_t e = run();
     if (e != hipSuccess) {
@@ -2684,14 +2458,14 @@ static int multi_finish_common(nps_multi *m, const double *offsets, double *d_ds
     if (m->broken) return fail(NPS_E_STATE, "an earlier pass failed on the device: nps_multi_reset first");
     HIP_TRY(hipSetDevice(m->device));
     if (normalise)
-        HIP_TRY(hipMemcpyAsync(m->d_offsets, offsets, sizeof(double) * m->S, hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(launch_multi_finish(m->stream, m->d_part, m->n, m->S, m->d_state, m->d_offsets, m->have_sums ? 1 : 0,
+        HIP_TRY(hipMemcpyAsync(m->d_offsets.get(), offsets, sizeof(double) * m->S, hipMemcpyHostToDevice, m->stream.get()));
+    HIP_TRY(launch_multi_finish(m->stream.get(), m->d_part.get(), m->n, m->S, m->d_state.get(), m->d_offsets.get(), m->have_sums ? 1 : 0,
                                 d_dst, normalise));
     std::vector<char> st(multi_state_bytes() * m->S);
-    HIP_TRY(hipMemcpyAsync(st.data(), m->d_state, st.size(), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), m->d_state.get(), st.size(), hipMemcpyDeviceToHost, m->stream.get()));
     if (h_scores_out && m->n)
-        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * m->n * m->S, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * m->n * m->S, hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
     if (nloci_out)
         for (int s = 0; s < m->S; ++s)
             memcpy(&nloci_out[s], st.data() + multi_state_bytes() * s, sizeof(uint64_t));  // first field
@@ -2701,7 +2475,7 @@ static int multi_finish_common(nps_multi *m, const double *offsets, double *d_ds
 extern "C" int nps_multi_finish(nps_multi *m, const double *offsets, double *scores_out, uint64_t *nloci_out) {
     if (!m) return fail(NPS_E_INVAL, "ctx is NULL");
     if (m->n && !scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
-    return multi_finish_common(m, offsets, m->d_scores, scores_out, nloci_out);
+    return multi_finish_common(m, offsets, m->d_scores.get(), scores_out, nloci_out);
 }
 
 extern "C" int nps_multi_finish_device(nps_multi *m, const double *offsets, double *d_scores_out,
@@ -2724,7 +2498,7 @@ extern "C" int nps_multi_partial_device(nps_multi *m, double *d_sums_out, uint64
 extern "C" int nps_multi_partial(nps_multi *m, double *sums_out, uint64_t *nloci_out) {
     if (!m) return fail(NPS_E_INVAL, "ctx is NULL");
     if (m->n && !sums_out) return fail(NPS_E_INVAL, "sums_out is NULL");
-    return multi_finish_common(m, nullptr, m->d_scores, sums_out, nloci_out, 0);
+    return multi_finish_common(m, nullptr, m->d_scores.get(), sums_out, nloci_out, 0);
 }
 
 extern "C" int nps_multi_timing(nps_multi *m, double *ms_params, double *ms_product, double *ms_fold) {
@@ -2747,14 +2521,14 @@ extern "C" int nps_profile_enable(nps_ctx *c, int on) {
 extern "C" int nps_profile_get(nps_ctx *c, nps_profile *out, int reset) {
     if (!c || !out) return fail(NPS_E_INVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     resolve_spans(c);
     *out = c->prof;
     if (reset) c->prof = nps_profile{};
     return NPS_OK;
 }
 
-extern "C" void *nps_stream(nps_ctx *c) { return c ? (void *)c->stream : nullptr; }
+extern "C" void *nps_stream(nps_ctx *c) { return c ? (void *)c->stream.get() : nullptr; }
 
 extern "C" int nps_fused_geometry(nps_ctx *c, int format, uint64_t n_rows, uint32_t *slices,
                                   uint32_t *teams, uint32_t *samples_per_slice) {

@@ -50,6 +50,18 @@ def test_no_cpu_fallback_without_device():
         capi.Cohort(6, 4)
 
 
+def test_failed_create_holds_no_resources():
+    """a device that does not exist (on a host without a GPU: any device) is refused with NPS_E_NODEVICE before anything
+    is allocated; where nothing is alive nps_live_resources() is 0"""
+    before = capi.live_resources()
+    if capi.device_count() == 0:
+        assert before == 0
+    with pytest.raises(capi.NpsError) as ei:
+        capi.Scorer(6, capi.make_params(), device=1 << 20)
+    assert ei.value.status == capi.E_NODEVICE
+    assert capi.live_resources() == before
+
+
 def test_product_never_imports_oracle():
     # the oracle is test infrastructure: nothing under nimpress_amd/ may reference it
     pkg = os.path.join(ROOT, "nimpress_amd")
