@@ -78,6 +78,9 @@ HOST_DIR = os.path.join(CSRC, "host")
 LIBHOST = os.path.join(PKG_DIR, "libnimpress_host.so")
 CLI = os.path.join(PKG_DIR, "nimpress")
 GXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wextra", "-ffp-contract=off"]
+# the host's translation units (the first two hold no libnps call: text and common parts, genotype file readers)
+HOST_SOURCES = ["nimpress_text.cpp", "nimpress_readers.cpp", "nimpress_scoring.cpp", "nimpress_hooks.cpp"]
+HOST_HEADERS = ["nimpress_host.hpp", "nimpress_internal.hpp"]
 
 
 def build_host(force: bool = False, verbose: bool = False) -> List[str]:
@@ -85,9 +88,9 @@ def build_host(force: bool = False, verbose: bool = False) -> List[str]:
     links libnps.so (rpath $ORIGIN) and zlib."""
     build_libnps(force=False, verbose=verbose)
     gxx = shutil.which("g++") or "g++"
-    srcs = [os.path.join(HOST_DIR, "nimpress_host.cpp")]
-    deps = srcs + [os.path.join(HOST_DIR, "nimpress_host.hpp"), LIBNPS,
-                   os.path.join(os.path.dirname(PKG_DIR), "include", "nps.h")]
+    srcs = [os.path.join(HOST_DIR, f) for f in HOST_SOURCES]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in HOST_HEADERS] + [
+        LIBNPS, os.path.join(os.path.dirname(PKG_DIR), "include", "nps.h")]
     link = ["-L" + PKG_DIR, "-lnps", "-lz", "-Wl,-rpath,$ORIGIN"]
     if force or _stale(LIBHOST, deps):
         cmd = [gxx] + GXX_FLAGS + ["-shared", "-o", LIBHOST] + srcs + link

@@ -1,6 +1,6 @@
 // main.cpp -- the `nimpress` command line (reference: src/nimpress.nim:652-757, docopt-driven).
 // Same usage text, options, defaults, version string, exit codes and output format; the work is
-// done by computePolygenicScores (nimpress_host.cpp) on top of libnps (HIP, MI355X).
+// done by computePolygenicScores (nimpress_scoring.cpp) on top of libnps (HIP, MI355X).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>

@@ -91,7 +91,7 @@ struct Variant {
     int32_t gtValue(size_t i) const;  // element i widened like bcf_get_genotypes does
 };
 
-struct IndexedSource;  // header + tabix / CSI index of an indexed file (nimpress_host.cpp)
+struct IndexedSource;  // header + tabix / CSI index of an indexed file (nimpress_readers.cpp)
 
 struct VCF {
     std::vector<std::string> samples;

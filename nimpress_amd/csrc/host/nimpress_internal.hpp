@@ -1,0 +1,72 @@
+// nimpress_internal.hpp -- what the host's translation units share with each other and with nobody else
+// (nimpress_text.cpp, nimpress_readers.cpp, nimpress_scoring.cpp, nimpress_hooks.cpp).  The interface of the host is
+// nimpress_host.hpp; the functions declared here are not exported from libnimpress_host.so.
+#pragma once
+#include "nimpress_host.hpp"
+
+#include <charconv>
+#include <cmath>
+#include <cstring>
+
+#pragma GCC visibility push(hidden)
+namespace nimpress {
+
+// ---- nimpress_text.cpp ----------------------------------------------------------------------------------
+std::vector<std::string> splitChar(const std::string &s, char sep);
+int64_t parseIntNim(const std::string &s);
+bool readFile(const std::string &path, std::string &out);
+double nowSeconds();
+
+// ---- nimpress_scoring.cpp: one score row through getImputedDosages' early returns (nim:523-585) -----------
+// What the reference decides about a row before it looks at a genotype, in its order: uncovered (nim:526-531), absent
+// (:533-551), FILTER (:553-558), else the effect allele's index (:375-379).
+struct RowClass {
+    int kind = 0;                // 0 = genotyped, else NPS_ROW_UNCOVERED / _ABSENT / _FILTERED
+    const Variant *v = nullptr;  // the record found (null for uncovered and absent rows)
+    int ref_is_effect = 0;
+    int eaidx = 0;               // genotyped rows: 0 = REF, k = ALT[k - 1]
+    int code_map = 0;            // genotyped .bed / .pgen rows: the NPS_MAP_* that makes the 2-bit code an effect allele count
+    std::string filter;          // FILTER of a filtered row's record (for the warning text)
+    std::string pre_warning;     // emitted before the row's own warning (coverage contig, one FORMAT/DS value per sample)
+};
+RowClass classifyRow(const ScoreEntry &e, bool restrictToCoveredRgns, const GenomeIntervals &coveredIvals,
+                     const RecordIndex &index, bool ignoreFilterField);
+// the reference's warnings of one row (nim:527-579): the pre-warning, then at most one of the five texts.  neffect is
+// the effect allele count as tallied (a float64 sum for FORMAT/DS rows: the test takes it rounded, the text prints
+// neffect / nobs as it stands); over_maxmis is the caller's nim:565 decision.
+void writeRowWarnings(Log &log, const ScoreEntry &e, int kind, const std::string &filter, const std::string &pre_warning,
+                      int64_t nsamples, uint64_t nmissing, double neffect, bool over_maxmis, double afMismatchPthresh);
+
+}  // namespace nimpress
+#pragma GCC visibility pop
+
+namespace nimpress {
+// formatFloat into buf (at most 32 characters): their number.  Inline: the matrix writer formats millions of values.
+inline size_t formatFloatTo(double x, char *buf) {
+    if (std::isnan(x)) {
+        memcpy(buf, "nan", 3);
+        return 3;
+    }
+    if (std::isinf(x)) {
+        const size_t n = x > 0 ? 3 : 4;
+        memcpy(buf, x > 0 ? "inf" : "-inf", n);
+        return n;
+    }
+    char *end = std::to_chars(buf, buf + 30, x, std::chars_format::general, 16).ptr;
+    bool plain = true;
+    for (const char *p = buf; p < end; ++p) plain = plain && *p != '.' && *p != 'e' && *p != 'n';
+    if (plain) {
+        *end++ = '.';
+        *end++ = '0';
+    }
+    return (size_t)(end - buf);
+}
+
+// (default visibility: its inline destructor is among the library's weak symbols)
+struct Tick {  // adds the scope's wall time to one of the Timings fields
+    double &acc;
+    double t0;
+    explicit Tick(double &a) : acc(a), t0(nowSeconds()) {}
+    ~Tick() { acc += nowSeconds() - t0; }
+};
+}  // namespace nimpress

@@ -249,26 +249,8 @@ def test_af_mismatch_warnings_at_default_afmisp_100k_samples(tmp_path):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import bcfwriter
+    from af_rows import ROWS as rows, expected_warnings   # the table and the oracle's texts: shared with the CPU test
     n = 100_000
-    # (pos, ref, ea, eaf, ALT allele count, missing samples, FILTER, in file?)
-    rows = [
-        (1000, "A", "C", 0.30, 60000, 0, [], True),        # exactly the expectation: p = 1
-        (1100, "A", "C", 0.30, 60050, 0, ["PASS"], True),  # near the mean: betacf -> NaN -> no warning
-        (1200, "A", "C", 0.30, 60600, 0, [], True),        # p = 0.0034
-        (1300, "A", "C", 0.30, 60700, 0, [], True),        # p = 0.00065 -> warned
-        (1400, "A", "C", 0.30, 59300, 0, [], True),        # p = 0.00063 -> warned (x below the mean)
-        (1500, "A", "C", 0.30, 59400, 0, [], True),        # p = 0.0034
-        (1600, "G", "C", 0.10, 40000, 0, [], True),        # far off: p = 0 -> warned
-        (1700, "A", "A", 0.70, 60700, 0, [], True),        # effect allele = REF, 139 300 REF alleles: warned
-        (1800, "A", "C", 0.30, 0, 0, [], False),           # absent, eaf 0.3: "cohort EAF is 0" warned
-        (1900, "A", "C", 1e-7, 0, 0, [], False),           # absent, eaf 1e-7: p = 1
-        (2000, "A", "C", float("nan"), 90000, 0, [], True),  # eaf NaN: no test
-        (2100, "A", "C", 0.30, 10000, 10000, [], True),    # 10 % missing: over --maxmis, no AF test
-        (2200, "A", "C", 0.30, 60120, 1000, [], True),     # 1 % missing: 198 000 trials, p = 0.00042 -> warned
-        (2300, "A", "C", 0.30, 60000, 1000, [], True),     # 1 % missing: p = 0.0033
-        (2400, "A", "C", 0.30, 10000, 0, ["FAIL"], True),  # FILTER: locus-imputed, no AF test
-        (2500, "A", "G", 0.30, 60700, 0, [], True),        # ea not among the ALT alleles -> absent -> warned
-    ]
     lines = ["af-mismatch", "", "", "GRCh37", "0.5"]
     recs = []
     for pos, ref, ea, eaf, x, nmiss, filt, present in rows:
@@ -291,30 +273,7 @@ def test_af_mismatch_warnings_at_default_afmisp_100k_samples(tmp_path):
     assert sum(1 for l in r.stdout.splitlines() if not l.startswith("WARN ")) == n
 
     # the oracle's decisions and texts, in score-file order
-    fmt = refcpu.format_score
-    expected, n_nan = [], 0
-    for pos, ref, ea, eaf, x, nmiss, filt, present in rows:
-        var = "7:%d:%s:%s" % (pos, ref, ea)
-        if not present or (ea != ref and ea != "C"):       # findVariant returns nil (nim:536-541)
-            if eaf == eaf and refcpu.binom_test(0, 2 * n, eaf) < 0.001:
-                expected.append("Variant %s cohort EAF is 0 in %d samples.  This is highly unlikely given "
-                                "polygenic score EAF of %s" % (var, n, fmt(eaf)))
-            continue
-        if filt == ["FAIL"]:
-            expected.append('Variant %s has a FILTER flag set (value "FAIL").  Imputing all dosages at this locus.' % var)
-            continue
-        if nmiss / n > 0.05:
-            expected.append("Locus 7:%d-%d has %s%% of samples missing a genotype. This exceeds the missingness "
-                            "threshold; imputing all dosages at this locus." % (pos, pos, fmt(nmiss / n * 100)))
-            continue
-        neff = (2 * (n - nmiss) - x) if ea == ref else x   # tallyAlleles counts the EFFECT allele
-        nobs = (n - nmiss) * 2
-        if eaf == eaf:
-            p = refcpu.binom_test(neff, nobs, eaf)
-            n_nan += int(p != p)
-            if p < 0.001:
-                expected.append("Variant %s cohort EAF is %s in %d samples.  This is highly unlikely given "
-                                "polygenic score EAF of %s" % (var, fmt(neff / nobs), n, fmt(eaf)))
+    expected, n_nan = expected_warnings(rows, n)
     assert n_nan == 1                                      # the MAXIT case really is in the fixture
     assert sum("cohort EAF is" in w for w in expected) == 7
     assert warns == expected

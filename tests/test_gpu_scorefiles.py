@@ -136,6 +136,44 @@ def test_one_pass_multi_equals_file_by_file(cohort_vcf):
             assert_within_bar(s1, ref, f, ref_nloci, "file by file: " + f)
 
 
+def test_one_pass_multi_equals_file_by_file_under_a_coverage_bed(tmp_path):
+    """the seam test_one_pass_multi_equals_file_by_file leaves out: --cov.  Two score files over set1.vcf.gz (6 samples)
+    -- set1.score and a copy with other betas and two rows fewer -- with set1.bed and with a BED that lacks contig 3:
+    per file the one-pass path logs exactly the lines of the file-by-file path ("is not covered", the coverage contig's
+    pre-warning before it, and at --afmisp=1 an AF-mismatch line for every genotyped or absent row with p < 1), counts
+    the same loci and gives the oracle's scores"""
+    vcf_path = os.path.join(G, "set1.vcf.gz")
+    set1 = os.path.join(G, "set1.score")
+    lines = open(set1).read().splitlines()
+    other = str(tmp_path / "other.score")
+    rows = [l.split("\t") for l in lines[5:] if not l.startswith(("1\t200\t", "2\t400\t"))]
+    assert len(rows) == len(lines) - 7
+    open(other, "w").write("\n".join(lines[:4] + ["-0.5"] + ["\t".join(r[:4] + [repr(0.07 * (k + 1) * (-1) ** k), r[5]])
+                                                           for k, r in enumerate(rows)]) + "\n")
+    no3 = str(tmp_path / "no3.bed")
+    open(no3, "w").write("".join(l + "\n" for l in open(os.path.join(G, "set1.bed")).read().splitlines()
+                                 if l.split("\t")[0] != "3"))
+    vcf = refcpu.read_vcf(vcf_path)
+    files = [set1, other]
+    kw = dict(maxmis=1.0, imp_sample="ps", afmisp=1.0)
+    seen = []
+    for cov in (os.path.join(G, "set1.bed"), no3):
+        got, nloci, logs = host.compute_polygenic_scores_multi(files, vcf_path, cov=cov, max_samples=64, **kw)
+        assert got.shape == (2, 6)
+        for i, f in enumerate(files):
+            s1, n1, log1 = host.compute_polygenic_scores(f, vcf_path, cov=cov, max_samples=64, **kw)
+            assert logs[i] == log1, (f, cov, logs[i], log1)
+            assert nloci[i] == n1, (f, cov)
+            ref, ref_nloci, _ = refcpu.compute_polygenic_scores(refcpu.read_score_file(f), vcf, True, refcpu.read_bed(cov),
+                                                                "ps", "homref", "ps", 1.0, 100, False)
+            assert n1 == ref_nloci
+            assert_within_bar(got[i], ref, f, ref_nloci, "one pass: " + f)
+            assert_within_bar(s1, ref, f, ref_nloci, "file by file: " + f)
+            seen += log1
+    assert any("is not covered by the sequence coverage BED" in l for l in seen)      # (not passed on empty logs)
+    assert any("Contig 3 not present within the coverage BED file." in l for l in seen)
+
+
 def test_results_left_in_device_memory_equal_the_host_copies(cohort_vcf):
     """what the multi-GPU exchange reads (tools/score_many.py with RCCL): nh_compute_dev / nh_compute_multi_dev leave
     the scores -- or, rows sharded, a block's un-normalised sums -- in DEVICE memory (nps_finish_device,

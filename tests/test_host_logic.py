@@ -55,6 +55,12 @@ def host():
     L.nh_betai.restype = C.c_double
     L.nh_betai.argtypes = [C.c_double] * 3
     L.nh_format_float.argtypes = [C.c_double, C.c_char_p, C.c_long]
+    L.nh_classify.restype = C.c_long
+    L.nh_classify.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_char_p, C.c_long]
+    L.nh_row_warnings.restype = C.c_long
+    L.nh_row_warnings.argtypes = [C.c_char_p, C.c_long, C.c_char_p, C.c_char_p, C.c_double, C.c_int, C.c_char_p, C.c_char_p,
+                                  C.c_long, C.c_long, C.c_double, C.c_int, C.c_double, C.c_char_p, C.c_long]
     return L
 
 
@@ -736,9 +742,8 @@ def test_ingest_under_sanitizers(tmp_path, san):
     exe = str(tmp_path / "ingest")
     cmd = [gxx, "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=" + san, "-fno-omit-frame-pointer", "-o", exe,
            os.path.join(ROOT, "tests", "native", "ingest_driver.cpp"),
-           os.path.join(ROOT, "nimpress_amd", "csrc", "host", "nimpress_host.cpp"),
-           "-L" + os.path.join(ROOT, "nimpress_amd"), "-lnps", "-lz",
-           "-Wl,-rpath," + os.path.join(ROOT, "nimpress_amd")]
+           os.path.join(ROOT, "nimpress_amd", "csrc", "host", "nimpress_text.cpp"),
+           os.path.join(ROOT, "nimpress_amd", "csrc", "host", "nimpress_readers.cpp"), "-lz"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0 and "sanitize" in r.stderr:
         pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
@@ -932,3 +937,130 @@ def test_ds16_codes_are_the_parser_s_float32_for_every_decimal():
             if k % 10 ** (4 - d) == 0:
                 assert v == np.float32("%.*f" % (d, k / 10000.0)), (k, d)
     assert np.isnan(refcpu.ds16_value(0xffff))
+
+
+# ------------------------------------------------------------------------------------------
+# the row classifier and the warning writer both scoring drivers call (nh_classify, nh_row_warnings)
+def _row_warnings(host, contig, pos, ref, ea, eaf, kind, filt, pre, n, nmiss, neff, over_maxmis, afmisp):
+    out = C.create_string_buffer(4096)
+    k = host.nh_row_warnings(contig.encode(), pos, ref.encode(), ea.encode(), eaf, kind, filt.encode(), pre.encode(), n,
+                             nmiss, float(neff), int(over_maxmis), afmisp, out, len(out))
+    assert k >= 0, host.nh_last_error()
+    lines = out.value.decode().split("\n")
+    assert len(lines) == k + 1 and lines[-1] == "" and all(l.startswith("WARN ") for l in lines[:-1])
+    return [l[5:] for l in lines[:-1]]
+
+
+def test_row_warning_writer_equals_the_oracle_on_the_af_mismatch_table(host):
+    """the one warning writer of the host (both scoring drivers call it) on the sixteen rows of
+    test_af_mismatch_warnings_at_default_afmisp_100k_samples, from the table's counts instead of a 100 000-sample BCF:
+    the lines, in order, are the texts the oracle's literal binomTest decides at the default --afmisp=0.001; an
+    uncovered row with and without the coverage contig's pre-warning; a FORMAT/DS row's non-integer allele sum"""
+    from af_rows import CONTIG, ROWS, ROW_FILTERED, ROW_PRESENT, ROW_UNCOVERED, expected_warnings, row_state
+    n, afmisp, maxmis = 100_000, 0.001, 0.05
+    expected, n_nan = expected_warnings(ROWS, n, afmisp, maxmis)
+    got, host_nan = [], 0
+    for row in ROWS:
+        pos, ref, ea, eaf = row[:4]
+        kind, nmiss, neff = row_state(row, n)
+        over = kind == ROW_PRESENT and nmiss / n > maxmis
+        got += _row_warnings(host, CONTIG, pos, ref, ea, eaf, kind, "FAIL" if kind == ROW_FILTERED else "", "", n, nmiss,
+                             neff, over, afmisp)
+        if kind == ROW_PRESENT and not over and eaf == eaf:
+            p = host.nh_binom_test_fast(neff, 2 * (n - nmiss), eaf)
+            host_nan += int(p != p)
+    assert got == expected
+    assert n_nan == 1 and host_nan == 1                    # the MAXIT case really is in the fixture
+    assert sum("cohort EAF is" in w for w in got) == 7
+    # an uncovered row: the pre-warning (the BED lacks the contig) comes first
+    locus = "Locus 3:500-500 is not covered by the sequence coverage BED.  Imputing all dosages at this locus."
+    pre = "Contig 3 not present within the coverage BED file."
+    assert _row_warnings(host, "3", 500, "A", "G", 0.01, ROW_UNCOVERED, "", "", 6, 0, 0, False, 1.0) == [locus]
+    assert _row_warnings(host, "3", 500, "A", "G", 0.01, ROW_UNCOVERED, "", pre, 6, 0, 0, False, 1.0) == [pre, locus]
+    # a FORMAT/DS row: the allele sum is no integer.  The test is decided on the rounded count (60 700 of 200 000 at
+    # eaf 0.3 warns, 60 600 does not: rows 1300 and 1200 of the table), the EAF in the text is the sum over nobs as it is
+    fmt = refcpu.format_score
+    for neff in (60700.4, 60699.6, 60600.4):
+        want = []
+        if refcpu.binom_test(round(neff), 2 * n, 0.30) < afmisp:
+            want = ["Variant 7:1300:A:C cohort EAF is %s in %d samples.  This is highly unlikely given polygenic score "
+                    "EAF of %s" % (fmt(neff / (2 * n)), n, fmt(0.30))]
+        assert _row_warnings(host, CONTIG, 1300, "A", "C", 0.30, ROW_PRESENT, "", "", n, 0, neff, False, afmisp) == want
+        assert bool(want) == (round(neff) == 60700)
+    assert fmt(60700.4 / (2 * n)) != fmt(60700 / (2 * n))
+
+
+def _classify(host, score, geno, bed=None, ignorefilt=False):
+    n = len(refcpu.read_score_file(score).entries)
+    kind, eaidx, rie, cmap = (np.full(n, -9, np.int32) for _ in range(4))
+    filt = C.create_string_buffer(1024)
+    got = host.nh_classify(score.encode(), geno.encode(), bed.encode() if bed else None, int(ignorefilt), n,
+                           kind.ctypes.data, eaidx.ctypes.data, rie.ctypes.data, cmap.ctypes.data, filt, len(filt))
+    assert got == n, host.nh_last_error()
+    filters = filt.value.decode().split("\n")[:-1]
+    assert len(filters) == n
+    return kind.tolist(), eaidx.tolist(), rie.tolist(), cmap.tolist(), filters
+
+
+def test_row_classifier_matches_oracle_and_picks_the_plink_code_maps(host, tmp_path):
+    """the one row classifier of the host (both scoring drivers call it): uncovered -> absent -> FILTER -> effect allele
+    index, in the reference's order (nim:526-561, 375-379), row by row against the oracle's is_variant_covered /
+    find_variant on set1 -- without a BED, with set1.bed and with a BED that lacks contig 3, with and without
+    --ignorefilt; and the code map of .bed (A1 / A2) and fixed-width .pgen (ALT / REF) records"""
+    score_path, vcf_path = os.path.join(G, "set1.score"), os.path.join(G, "set1.vcf.gz")
+    score = refcpu.read_score_file(score_path)
+    vcf = refcpu.read_vcf(vcf_path)
+    no3 = str(tmp_path / "no3.bed")
+    open(no3, "w").write("".join(l + "\n" for l in open(os.path.join(G, "set1.bed")).read().splitlines()
+                                 if l.split("\t")[0] != "3"))
+    loci = ["%s:%d" % (e.contig, e.pos) for e in score.entries]
+    for bed_path in (None, os.path.join(G, "set1.bed"), no3):
+        bed = refcpu.read_bed(bed_path) if bed_path else None
+        for ignorefilt in (False, True):
+            kind, eaidx, rie, _, filters = _classify(host, score_path, vcf_path, bed_path, ignorefilt)
+            for i, e in enumerate(score.entries):
+                rec = None
+                if bed is not None and not refcpu.is_variant_covered(e, bed):
+                    want = 1                                            # NPS_ROW_UNCOVERED
+                else:
+                    rec = refcpu.find_variant(vcf, e)
+                    want = 2 if rec is None else 3 if not ignorefilt and rec.filt not in (".", "PASS") else 0
+                assert kind[i] == want, (bed_path, ignorefilt, loci[i])
+                assert rie[i] == int(e.refseq == e.easeq)
+                assert filters[i] == (rec.filt if want == 3 else "")
+                if want == 0:
+                    assert eaidx[i] == (0 if e.refseq == e.easeq else rec.alts.index(e.easeq) + 1)
+            if bed_path is None:
+                assert kind[loci.index("1:150")] == (0 if ignorefilt else 3)
+                assert eaidx[loci.index("1:300")] == 2 and kind[loci.index("1:300")] == 0       # GA -> CT: the second ALT
+                assert (kind[0], eaidx[0], rie[0]) == (0, 0, 1) and loci[0] == "1:100"          # A -> A
+                assert kind[loci.index("1:200")] == 2                                          # T is not an ALT allele
+            if bed_path == no3:
+                assert kind[loci.index("3:500")] == 1
+            if bed_path == os.path.join(G, "set1.bed"):
+                assert [int(k == 1) for k in kind] == [1, 0, 0, 1, 1, 0]
+    # PLINK 1 .bed (A1 = the .bim line's fifth column, A2 its sixth) and PLINK 2 fixed-width .pgen: 8 samples, 4 variants
+    import pgenwriter
+    rng = np.random.default_rng(3)
+    n, m = 8, 4
+    names = ["P%d" % i for i in range(n)]
+    variants = [("1", 100 + 10 * j, "v%d" % j, "A", "G") for j in range(m)]          # (contig, pos, id, REF, ALT)
+    alt = rng.integers(0, 3, size=(m, n))
+    pgenwriter.write_pgen(str(tmp_path / "p"), names, variants, alt, np.zeros((m, n), bool))
+    (tmp_path / "b.bed").write_bytes(b"\x6c\x1b\x01" + bytes(rng.integers(0, 256, size=m * 2, dtype=np.uint8)))
+    (tmp_path / "b.bim").write_text("".join("%s\t%s\t0\t%d\t%s\t%s\n" % (c, i, p, a, r) for c, p, i, r, a in variants))
+    (tmp_path / "b.fam").write_text("".join("F %s 0 0 0 -9\n" % s for s in names))
+    head = ["t", "", "", "x", "0.0"]
+    ps = str(tmp_path / "plink.score")                     # effect allele = ALT / A1, then REF / A2; 1:130 is not listed
+    open(ps, "w").write("\n".join(head + ["1\t100\tA\tG\t0.1\t0.2", "1\t110\tA\tA\t0.1\t0.2", "1\t125\tA\tG\t0.1\t0.2"]))
+    NPS_MAP_BED_A2, NPS_MAP_BED_A1, NPS_MAP_PGEN_ALT, NPS_MAP_PGEN_REF = 0, 1, 2, 3    # include/nps.h
+    kind, eaidx, rie, cmap, _ = _classify(host, ps, str(tmp_path / "b.bed"))
+    assert kind == [0, 0, 2] and rie == [0, 1, 0] and eaidx[:2] == [1, 0]
+    assert cmap[:2] == [NPS_MAP_BED_A1, NPS_MAP_BED_A2]
+    kind, eaidx, rie, cmap, _ = _classify(host, ps, str(tmp_path / "p.pgen"))
+    assert kind == [0, 0, 2] and rie == [0, 1, 0] and eaidx[:2] == [1, 0]
+    assert cmap[:2] == [NPS_MAP_PGEN_ALT, NPS_MAP_PGEN_REF]
+    # a .bim has no REF: a score row that calls A1 its reference allele finds the record too, and counts A1
+    open(ps, "w").write("\n".join(head + ["1\t100\tG\tG\t0.1\t0.2", "1\t100\tG\tA\t0.1\t0.2"]))
+    kind, eaidx, rie, cmap, _ = _classify(host, ps, str(tmp_path / "b.bed"))
+    assert kind == [0, 0] and rie == [1, 0] and cmap == [NPS_MAP_BED_A1, NPS_MAP_BED_A2]

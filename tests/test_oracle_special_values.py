@@ -134,7 +134,7 @@ def test_score_file_spellings_parse_alike():
         a = refcpu.nim_parse_float(sp)
         end = ctypes.c_char_p()
         b = libc.strtod(sp.encode(), ctypes.byref(end))
-        assert end.value == b"", sp   # the whole field is consumed, as nimpress_host.cpp parseFloatNim demands
+        assert end.value == b"", sp   # the whole field is consumed, as nimpress_text.cpp parseFloatNim demands
         assert (np.isnan(a) and np.isnan(b)) or np.float64(a).tobytes() == np.float64(b).tobytes(), (sp, a, b)
     assert refcpu.nim_parse_float("1e400") == float("inf") and refcpu.nim_parse_float("4.9e-324") == 5e-324
 
