@@ -91,50 +91,16 @@ __global__ __launch_bounds__(256) void ds_params_kernel(const DsTally *__restric
         const double beta = desc[row].beta, eaf = desc[row].eaf;
         const bool rie = (desc[row].ref_is_effect & 1) != 0;       // homref imputation value
         const bool flip = desc[row].ref_is_effect == 1;            // dosage = 2 - DS
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const RowDecision d = decide_row(p, over_maxmis(nmiss, n_samples, p.max_missing_rate), eaf, rie, neff, ngen);
+        used = d.used;
         DsRowP r;
         r.beta = beta;
-        r.imp = 0.0;
-        r.cst = 0.0;
-        r.mode = 0;
+        r.imp = d.mode == 1 ? d.imp : 0.0;
+        r.cst = d.mode == 2 ? d.imp : 0.0;
+        r.mode = d.mode;
         r.rie = flip ? 1 : 0;
-        int reason;
-        const double missingrate = (double)nmiss / (double)n_samples;
-        if (missingrate > p.max_missing_rate) {  // nim:565-571
-            reason = NPS_REASON_MAXMIS;
-            if (p.imp_locus != NPS_LOCUS_IGNORE) {
-                r.cst = p.imp_locus == NPS_LOCUS_PS       ? eaf * 2.0
-                        : p.imp_locus == NPS_LOCUS_HOMREF ? (rie ? 2.0 : 0.0)
-                                                          : nan;
-                r.mode = 2;
-                used = 1;
-            }
-        } else {  // nim:450-481
-            reason = NPS_REASON_GENOTYPED;
-            used = 1;
-            r.mode = 1;
-            switch (p.imp_sample) {
-            case NPS_SAMPLE_PS: r.imp = eaf * 2.0; break;
-            case NPS_SAMPLE_HOMREF: r.imp = rie ? 2.0 : 0.0; break;
-            case NPS_SAMPLE_FAIL: r.imp = nan; break;
-            default:
-                if ((double)ngen >= p.min_cs)
-                    r.imp = neff / (double)ngen;
-                else
-                    r.imp = p.imp_sample == NPS_SAMPLE_INT_PS ? eaf * 2.0 : nan;
-                break;
-            }
-        }
         rowp[row] = r;
-        if (stats) {
-            nps_locus_stat s;
-            s.ngenotyped = ngen;
-            s.nmissing = nmiss;
-            s.neffect = neff;
-            s.used = used;
-            s.reason = reason;
-            stats[row] = s;
-        }
+        if (stats) stats[row] = row_stat(d, ngen, nmiss, neff);
     }
     const int cnt = __syncthreads_count(used);
     if (threadIdx.x == 0 && cnt) atomicAdd(nloci, (unsigned long long)cnt);

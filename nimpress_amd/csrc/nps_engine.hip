@@ -482,31 +482,10 @@ extern "C" int nps_reset(nps_ctx *c, const nps_params *params) {
 // rows without genotype data are decided entirely on the host: nimpress.nim:526-558 + 417-447
 static void host_locus_row(nps_ctx *c, int kind, int rie, double beta, double eaf,
                            nps_locus_stat *st) {
-    st->ngenotyped = 0;
-    st->nmissing = 0;
-    st->neffect = 0.0;
-    int used;
-    double dosage = 0.0;
-    if (kind == NPS_ROW_ABSENT) {  // :536-551
-        st->reason = NPS_REASON_ABSENT;
-        if (c->params.imp_missing == NPS_MISSING_HOMREF) {
-            used = 1;
-            dosage = rie ? 2.0 : 0.0;
-        } else {
-            used = 0;
-        }
-    } else {  // UNCOVERED :526-531, FILTERED :553-558 -> imputeLocusDosages :417-447
-        st->reason = kind == NPS_ROW_UNCOVERED ? NPS_REASON_UNCOVERED : NPS_REASON_FILTERED;
-        switch (c->params.imp_locus) {
-        case NPS_LOCUS_IGNORE: used = 0; break;
-        case NPS_LOCUS_PS: used = 1; dosage = eaf * 2.0; break;
-        case NPS_LOCUS_HOMREF: used = 1; dosage = rie ? 2.0 : 0.0; break;
-        default: used = 1; dosage = std::numeric_limits<double>::quiet_NaN(); break;
-        }
-    }
-    st->used = used;
-    if (used) {
-        volatile double term = dosage * beta;  // same product as nimpress.nim:640, not contracted
+    const RowDecision d = no_data_row(dev_params(c->params), kind, eaf, rie != 0);
+    *st = row_stat(d, 0, 0, 0.0);
+    if (d.used) {
+        volatile double term = d.imp * beta;  // same product as nimpress.nim:640, not contracted
         c->const_sum += term;
         c->host_nloci += 1;
     }
@@ -1576,21 +1555,6 @@ static int materialize_resident_stats(nps_ctx *c) {
     c->res_index.clear();
     c->res_host_stats.clear();
     return NPS_OK;
-}
-
-// the reference's test `nmissing / N > --maxmis` (double division, nimpress.nim:565) is monotone in nmissing: the largest
-// count that is NOT over the rate (-1: none), found with that very expression -- the kernels compare integers
-static int64_t maxmis_threshold(uint64_t n, double rate) {
-    if (n == 0 || (double)0 / (double)n > rate) return -1;
-    uint64_t lo = 0, hi = n;  // pred(lo) holds
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (!((double)mid / (double)n > rate))
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return (int64_t)lo;
 }
 
 // NPS_FMT_GT2X runs of a definition with special rows (mx_special): the fixed-point pass scored them at beta = eaf = 0 --

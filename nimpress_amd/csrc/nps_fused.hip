@@ -109,49 +109,19 @@ static __device__ __forceinline__ void row_lut(const FusedArgs &a, unsigned long
                                                double (&v)[4], int &used) {
     const uint64_t nmiss = (x >> 28) & 0xFFFFFFFull, neff = x & 0xFFFFFFFull;
     const uint64_t ngen = a.n_samples - nmiss;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    int reason;
-    used = 0;
+    const RowDecision d = decide_row(a.prm, over_maxmis(nmiss, a.n_samples, a.prm.max_missing_rate), eaf, rie,
+                                     (double)neff, ngen);
+    used = d.used;
     v[0] = v[1] = v[2] = v[3] = 0.0;
-    const double missingrate = (double)nmiss / (double)a.n_samples;
-    if (missingrate > a.prm.max_missing_rate) {
-        reason = NPS_REASON_MAXMIS;
-        if (a.prm.imp_locus != NPS_LOCUS_IGNORE) {
-            const double c = a.prm.imp_locus == NPS_LOCUS_PS       ? eaf * 2.0
-                             : a.prm.imp_locus == NPS_LOCUS_HOMREF ? (rie ? 2.0 : 0.0)
-                                                                   : nan;
-            used = 1;
-            v[0] = v[1] = v[2] = v[3] = c * beta;
-        }
-    } else {
-        reason = NPS_REASON_GENOTYPED;
-        used = 1;
-        double imp;
-        switch (a.prm.imp_sample) {
-        case NPS_SAMPLE_PS: imp = eaf * 2.0; break;
-        case NPS_SAMPLE_HOMREF: imp = rie ? 2.0 : 0.0; break;
-        case NPS_SAMPLE_FAIL: imp = nan; break;
-        default:
-            if ((double)ngen >= a.prm.min_cs)
-                imp = (double)neff / (double)ngen;
-            else
-                imp = a.prm.imp_sample == NPS_SAMPLE_INT_PS ? eaf * 2.0 : nan;
-            break;
-        }
+    if (d.mode == 2) {
+        v[0] = v[1] = v[2] = v[3] = d.imp * beta;
+    } else if (d.mode == 1) {
         v[0] = 0.0 * beta;  // indexed by CODE: 0, 1 = dosage ; 2 = missing ; 3 = dosage 2
         v[1] = 1.0 * beta;
-        v[2] = imp * beta;
+        v[2] = d.imp * beta;
         v[3] = 2.0 * beta;
     }
-    if (write_stats) {
-        nps_locus_stat s;
-        s.ngenotyped = ngen;
-        s.nmissing = nmiss;
-        s.neffect = (double)neff;
-        s.used = used;
-        s.reason = reason;
-        a.stats[row] = s;
-    }
+    if (write_stats) a.stats[row] = row_stat(d, ngen, nmiss, (double)neff);
 }
 
 // ---------------------------------------------------------------------------------------------

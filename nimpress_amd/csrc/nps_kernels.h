@@ -6,6 +6,7 @@
 
 #include "../../include/nps.h"
 #include "nps_mx_route.h"
+#include "nps_row_decision.h"  // DevParams and the per-row decisions every kernel shares
 
 namespace nps {
 
@@ -50,12 +51,6 @@ static inline uint64_t stride_words_for(uint64_t n_samples) {
     if (w == 0) w = 1;
     return (w + kStrideAlignWords - 1) / kStrideAlignWords * kStrideAlignWords;
 }
-
-struct DevParams {
-    int32_t imp_locus, imp_missing, imp_sample;
-    double max_missing_rate;
-    double min_cs;  // compared in double, nimpress.nim:471
-};
 
 // raw GT buffer (device copy; elem_bytes 4 = bcf_get_genotypes int32, 1 / 2 = the int8 / int16 vector
 // of a BCF record) -> row `row_in_group` of the group at d_group (group interleaved layout) + tally

@@ -362,49 +362,17 @@ __global__ __launch_bounds__(256) void row_params_kernel(
             const uint64_t ngen = n_samples - nmiss;
             const double beta = desc[row].beta, eaf = desc[row].eaf;
             const bool rie = desc[row].ref_is_effect != 0;
-            const double nan = __longlong_as_double(0x7ff8000000000000ll);
-            int reason;
-            const double missingrate = (double)nmiss / (double)n_samples;
-            if (missingrate > p.max_missing_rate) {  // :565-571
-                reason = NPS_REASON_MAXMIS;
-                if (p.imp_locus == NPS_LOCUS_IGNORE) {
-                    used = 0;
-                } else {
-                    const double c = p.imp_locus == NPS_LOCUS_PS       ? eaf * 2.0
-                                     : p.imp_locus == NPS_LOCUS_HOMREF ? (rie ? 2.0 : 0.0)
-                                                                       : nan;
-                    used = 1;
-                    v0 = v1 = v2 = v3 = c * beta;
-                }
-            } else {  // :582-585
-                reason = NPS_REASON_GENOTYPED;
-                used = 1;
-                double imp;
-                switch (p.imp_sample) {
-                case NPS_SAMPLE_PS: imp = eaf * 2.0; break;
-                case NPS_SAMPLE_HOMREF: imp = rie ? 2.0 : 0.0; break;
-                case NPS_SAMPLE_FAIL: imp = nan; break;
-                default:
-                    if ((double)ngen >= p.min_cs)
-                        imp = (double)neff / (double)ngen;
-                    else
-                        imp = p.imp_sample == NPS_SAMPLE_INT_PS ? eaf * 2.0 : nan;
-                    break;
-                }
+            const RowDecision d = decide_row(p, over_maxmis(nmiss, n_samples, p.max_missing_rate), eaf, rie, (double)neff, ngen);
+            used = d.used;
+            if (d.mode == 2) {
+                v0 = v1 = v2 = v3 = d.imp * beta;
+            } else if (d.mode == 1) {
                 v0 = 0.0 * beta;  // LUT is indexed by CODE: 0, 1 = dosage ; 2 = missing ; 3 = dosage 2
                 v1 = 1.0 * beta;
-                v2 = imp * beta;
+                v2 = d.imp * beta;
                 v3 = 2.0 * beta;
             }
-            if (stats) {
-                nps_locus_stat s;
-                s.ngenotyped = ngen;
-                s.nmissing = nmiss;
-                s.neffect = (double)neff;
-                s.used = used;
-                s.reason = reason;
-                stats[row] = s;
-            }
+            if (stats) stats[row] = row_stat(d, ngen, nmiss, (double)neff);
         }
         double4 *l4 = reinterpret_cast<double4 *>(lut + row * 4);
         *l4 = make_double4(v0, v1, v2, v3);

@@ -332,7 +332,6 @@ __global__ __launch_bounds__(256) void multi_params_kernel(
                     table[(((((sb * 2 + (f >> 1)) * T + (c >> 4)) * 2 + dm) * 64 + (c & 15) + 16 * g) << 2) + 2 * (f & 1) + wi] = 0;
         return;
     }
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
     const int fx = F[s];
     uint32_t frag[2][8][4];  // [matrix][digit][prefix f]: byte b = the coefficient digit of (byte b, prefix f)
 #pragma unroll
@@ -359,46 +358,23 @@ __global__ __launch_bounds__(256) void multi_params_kernel(
             double wD = 0.0, wM = 0.0, cst = 0.0;  // weights of the dosage / the is-missing matrix; constant
             int used = 0, has_const = 0;
             const bool rie = d.ref_is_effect != 0;
-            auto locus = [&]() {  // imputeLocusDosages nimpress.nim:417-447
-                if (p.imp_locus == NPS_LOCUS_IGNORE) return;
-                used = 1;
-                has_const = 1;
-                cst = (p.imp_locus == NPS_LOCUS_PS ? d.eaf * 2.0 : p.imp_locus == NPS_LOCUS_HOMREF ? (rie ? 2.0 : 0.0) : nan) *
-                      d.beta;
-            };
+            RowDecision dec{0, 0, 0, 0.0};  // NPS_ROW_NOT_IN_SCORE: the row is not part of this score
             if (d.kind == NPS_ROW_PRESENT) {
                 const unsigned long long t = tally[j];
                 const uint64_t nmiss = t >> 32, neff = t & 0xffffffffull, ngen = n_samples - nmiss;
-                const double missingrate = (double)nmiss / (double)n_samples;
-                if (missingrate > p.max_missing_rate) {  // :565-571
-                    locus();
-                } else {  // :582-585 -> imputeSampleDosages :450-481
-                    used = 1;
-                    double imp;
-                    switch (p.imp_sample) {
-                    case NPS_SAMPLE_PS: imp = d.eaf * 2.0; break;
-                    case NPS_SAMPLE_HOMREF: imp = rie ? 2.0 : 0.0; break;
-                    case NPS_SAMPLE_FAIL: imp = nan; break;
-                    default:
-                        if ((double)ngen >= p.min_cs)
-                            imp = (double)neff / (double)ngen;
-                        else
-                            imp = p.imp_sample == NPS_SAMPLE_INT_PS ? d.eaf * 2.0 : nan;
-                        break;
-                    }
-                    wD = d.beta;
-                    // a missing genotype has code 3: it already got 3 x beta from the dosage matrix
-                    wM = imp * d.beta - 3.0 * d.beta;
-                }
-            } else if (d.kind == NPS_ROW_ABSENT) {  // :536-551
-                if (p.imp_missing == NPS_MISSING_HOMREF) {
-                    used = 1;
-                    has_const = 1;
-                    cst = (rie ? 2.0 : 0.0) * d.beta;
-                }
-            } else if (d.kind == NPS_ROW_UNCOVERED || d.kind == NPS_ROW_FILTERED) {  // :526-531, :553-558
-                locus();
-            }  // else: the row is not part of this score
+                dec = decide_row(p, over_maxmis(nmiss, n_samples, p.max_missing_rate), d.eaf, rie, (double)neff, ngen);
+            } else if (d.kind == NPS_ROW_ABSENT || d.kind == NPS_ROW_UNCOVERED || d.kind == NPS_ROW_FILTERED) {
+                dec = no_data_row(p, d.kind, d.eaf, rie);
+            }
+            used = dec.used;
+            if (dec.mode == 1) {
+                wD = d.beta;
+                // a missing genotype has code 3: it already got 3 x beta from the dosage matrix
+                wM = dec.imp * d.beta - 3.0 * d.beta;
+            } else if (dec.mode == 2) {
+                has_const = 1;
+                cst = dec.imp * d.beta;
+            }
             const bool m_nan = !(fabs(wM) < __builtin_huge_val());  // NaN, or an infinite eaf: llrint(inf) is undefined
             VD[f] = llrint(ldexp(wD, fx));
             VM[f] = m_nan ? 0ll : llrint(ldexp(wM, fx));

@@ -149,22 +149,17 @@ static __device__ __forceinline__ void mx_row(const MxArgs &a, unsigned long lon
     if (!live) return;
     const uint32_t nmiss = (uint32_t)(x >> 28) & 0xFFFFFFFu, neff = (uint32_t)x & 0xFFFFFFFu;  // (both < 2^28)
     const uint32_t ngen = (uint32_t)a.n_samples - nmiss;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    int reason;
+    RowDecision d{0, NPS_REASON_MAXMIS, 0, 0.0};  // (only used and reason are kept here: the operands below are the row's weights)
     if ((int64_t)nmiss > a.t_maxmis) {  // == (double)nmiss / (double)N > --maxmis, t_maxmis found with that very division
-        reason = NPS_REASON_MAXMIS;
         if (a.prm.imp_locus != NPS_LOCUS_IGNORE) {  // (rare: the row's score entry is fetched here)
             const double beta = a.desc[row].beta, eaf = a.desc[row].eaf;
             const bool rie = a.desc[row].ref_is_effect != 0;
-            const double c = a.prm.imp_locus == NPS_LOCUS_PS       ? eaf * 2.0
-                             : a.prm.imp_locus == NPS_LOCUS_HOMREF ? (rie ? 2.0 : 0.0)
-                                                                   : nan;
-            used = 1;
-            cst = c * beta;
+            d.used = locus_dosage(a.prm, eaf, rie, d.imp);
+            cst = d.imp * beta;
         }
     } else {
-        reason = NPS_REASON_GENOTYPED;
-        used = 1;
+        d.reason = NPS_REASON_GENOTYPED;
+        d.used = 1;
         // the common path without branches: the internal imputation value is worked out for every row and
         // selected (the control wave's step waits for exactly this chain of dependent operations)
         const bool internal = a.prm.imp_sample == NPS_SAMPLE_INT_PS || a.prm.imp_sample == NPS_SAMPLE_INT_FAIL;
@@ -186,17 +181,10 @@ static __device__ __forceinline__ void mx_row(const MxArgs &a, unsigned long lon
             wme[i] = dead ? 0u : e[i];
             wmo[i] = dead ? 0u : o[i];
         }
-        if (dead) cst = nan;
+        if (dead) cst = row_nan();
     }
-    if (write_stats) {
-        nps_locus_stat s;
-        s.ngenotyped = ngen;
-        s.nmissing = nmiss;
-        s.neffect = (double)neff;
-        s.used = used;
-        s.reason = reason;
-        a.stats[row] = s;
-    }
+    used = d.used;
+    if (write_stats) a.stats[row] = row_stat(d, ngen, nmiss, (double)neff);
 }
 
 
