@@ -85,9 +85,7 @@ struct nps_cohort {
     std::atomic<bool> mx_tally_asked{false};
     std::mutex tally_mutex;  // NPS_MODE_AUTO may count them lazily from whichever context scores the cohort first
     std::atomic<uint32_t> expect_passes{0};  // nps_cohort_expect_passes: how often the caller will score this cohort (0: not said)
-    PinnedBuf h_push[2];  // the ring of nps_cohort_push_* (grown together; [1] is allocated last: its size is the ring's)
-    Event ev_push[2];     // ([1] is created last, after d_push_tally: it stands for "the push state is complete")
-    int push_next = 0;
+    StagingRing push{2};  // the ring of nps_cohort_push_* (grows to the widest row pushed)
     DevBuf<unsigned long long> d_push_tally;  // scratch word for the decode kernel's tally (a GT2 cohort keeps none)
     // NPS_FMT_DS32: rows that hold a value outside [0, 2] (checked when rows are uploaded; the generator clips): while
     // there is one, the cohort is scored by the two-pass kernels (the single-read kernel's fixed-point tallies need the range)
@@ -151,6 +149,13 @@ struct PendingRow {
     nps_locus_stat host;
 };
 
+// the rows pushed since the last run_batch, GT or FORMAT/DS: what the host knows of them and, after the run, their statistics
+struct OpenBatch {
+    uint32_t cap = 0, rows = 0;
+    nps_row_desc *h_desc = nullptr;     // pinned [cap]
+    nps_locus_stat *h_stats = nullptr;  // pinned [cap]
+};
+
 struct MxOpRow {  // nps_mxg.hip (tallies given): the weight operands of one row
     unsigned char bytes[48];
 };
@@ -164,42 +169,30 @@ struct nps_ctx {
     nps_params params{};
 
     // streaming batch
-    uint32_t batch_cap = 0, batch_rows = 0;
-    DevBuf<uint32_t> d_codes;               // [batch_cap/4 groups][stride_words][4] (interleaved)
-    DevBuf<unsigned long long> d_tally;     // [batch_cap]
-    DevBuf<nps_row_desc> d_desc;            // [batch_cap]
-    nps_row_desc *h_desc = nullptr;         // pinned [batch_cap]
-    DevBuf<double> d_lut;                   // [batch_cap][4]
-    DevBuf<nps_locus_stat> d_stats;         // [batch_cap]
-    nps_locus_stat *h_stats = nullptr;      // pinned [batch_cap]
-    static constexpr int kRawSlots = 8;  // rows in flight between the caller's buffer and the device
-    int32_t *h_raw[kRawSlots] = {};  // pinned staging ring for caller buffers
-    PinnedBuf h_arena;  // ONE pinned allocation holding h_result, h_desc, h_stats and h_raw[]
-    Event ev_raw[kRawSlots];
-    int raw_next = 0;
+    OpenBatch gt;
+    DevBuf<uint32_t> d_codes;               // [gt.cap/4 groups][stride_words][4] (interleaved)
+    DevBuf<unsigned long long> d_tally;     // [gt.cap]
+    DevBuf<nps_row_desc> d_desc;            // [gt.cap]
+    DevBuf<double> d_lut;                   // [gt.cap][4]
+    DevBuf<nps_locus_stat> d_stats;         // [gt.cap]
+    PinnedBuf h_arena;      // ONE pinned allocation holding h_result, gt.h_desc and gt.h_stats
+    StagingRing raw{8};     // diploid GT, packed and .bed rows in flight between the caller's buffer and the device
 
-    // FORMAT/DS streaming batch (allocated on the first nps_push_ds)
-    uint32_t ds_cap = 0, ds_rows = 0;
+    // FORMAT/DS streaming batch (ensure_ds: allocated on the first row that needs it)
+    OpenBatch ds;
     uint64_t ds_stride_f = 0;
-    DevBuf<float> d_ds;                  // [ds_cap][ds_stride_f]
-    DevBuf<nps_row_desc> d_ds_desc;      // [ds_cap]
+    DevBuf<float> d_ds;                  // [ds.cap][ds_stride_f]
+    DevBuf<nps_row_desc> d_ds_desc;      // [ds.cap]
     DevBuf<DsTally> d_ds_tally;
     DevBuf<DsRowP> d_ds_rowp;
     DevBuf<nps_locus_stat> d_ds_stats;
-    PinnedBuf h_ds_arena;                // pinned: h_ds_desc, h_ds_stats, staging ring
-    nps_row_desc *h_ds_desc = nullptr;
-    nps_locus_stat *h_ds_stats = nullptr;
-    float *h_ds_raw[2] = {nullptr, nullptr};
-    Event ev_ds_raw[2];                  // ([1] is what ensure_ds creates last: it stands for "the DS batch is complete")
-    int ds_raw_next = 0;
+    PinnedBuf h_ds_arena;                // pinned: ds.h_desc, ds.h_stats
+    StagingRing ds_raw{2};               // rows of nps_push_ds
     // resident DS runs (grown on demand)
     DevBuf<DsTally> d_rds_tally;
     DevBuf<DsRowP> d_rds_rowp;
 
-    // raw GT staging for ploidy > 2: a ring of two pinned host buffers (grown together on demand), read by the kernel
-    PinnedBuf h_poly[2];  // ([1] is allocated last: its size is the ring's)
-    Event ev_poly[2];
-    int poly_next = 0;
+    StagingRing poly{2};  // raw GT records of ploidy > 2, read by the decode kernel (grows to the widest record pushed)
 
     // accumulators
     AccumGeom geom{};         // streaming geometry (groups_per_chunk for a full batch)
@@ -363,14 +356,14 @@ static void choose_geometry(nps_ctx *c) {
 static int zero_state(nps_ctx *c) {
     // d_part is not touched: chunks_used = 0 makes the first writer overwrite it
     HIP_TRY(hipMemsetAsync(c->d_nloci.get(), 0, 3 * sizeof(unsigned long long), c->stream.get()));
-    if (c->batch_rows)  // tallies of rows decoded into the open batch (the array is zero otherwise)
-        HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->batch_rows, c->stream.get()));
+    if (c->gt.rows)  // tallies of rows decoded into the open batch (the array is zero otherwise)
+        HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->gt.rows, c->stream.get()));
     c->chunks_used = 0;
     c->broken = false;
     c->const_sum = 0.0;
     c->host_nloci = 0;
-    c->batch_rows = 0;
-    c->ds_rows = 0;
+    c->gt.rows = 0;
+    c->ds.rows = 0;
     c->pending.clear();
     c->ready.clear();
     c->ready_cursor = 0;
@@ -415,46 +408,40 @@ extern "C" int nps_create(nps_ctx **out, int device, uint64_t n_samples, const n
     uint64_t cap = (64ull << 20) / (row_words * 4);
     cap = std::max<uint64_t>(16, std::min<uint64_t>(cap, 4096));
     cap = cap / 16 * 16;
-    c->batch_cap = (uint32_t)cap;
+    c->gt.cap = (uint32_t)cap;
     c->geom.groups_per_chunk =
-        std::max(1u, ((c->batch_cap / 4) + c->n_chunks - 1) / c->n_chunks);
+        std::max(1u, ((c->gt.cap / 4) + c->n_chunks - 1) / c->n_chunks);
 
     HIP_TRY(c->stream.create());
-    HIP_TRY(c->d_codes.alloc(row_words * c->batch_cap));
-    HIP_TRY(hipMemsetAsync(c->d_codes.get(), 0, row_words * 4 * c->batch_cap, c->stream.get()));
-    HIP_TRY(c->d_tally.alloc(c->batch_cap));
-    HIP_TRY(c->d_desc.alloc(c->batch_cap));
+    HIP_TRY(c->d_codes.alloc(row_words * c->gt.cap));
+    HIP_TRY(hipMemsetAsync(c->d_codes.get(), 0, row_words * 4 * c->gt.cap, c->stream.get()));
+    HIP_TRY(c->d_tally.alloc(c->gt.cap));
+    HIP_TRY(c->d_desc.alloc(c->gt.cap));
     {
-        // One pinned arena for all host staging, carved at 4 KiB boundaries, padded to 64 KiB.
+        // One pinned arena for the result block and the batch's host arrays, carved at 4 KiB boundaries, padded to 64 KiB.
         auto up = [](size_t v) { return (v + 4095) / 4096 * 4096; };
-        const size_t sz_desc = up(sizeof(nps_row_desc) * c->batch_cap);
-        const size_t sz_stats = up(sizeof(nps_locus_stat) * c->batch_cap);
-        const size_t sz_raw = up(sizeof(int32_t) * 2 * std::max<uint64_t>(c->n, 1));
-        size_t total = 4096 + sz_desc + sz_stats + nps_ctx::kRawSlots * sz_raw;
-        total = (total + 65535) / 65536 * 65536;
+        const size_t sz_desc = up(sizeof(nps_row_desc) * c->gt.cap);
+        const size_t sz_stats = up(sizeof(nps_locus_stat) * c->gt.cap);
+        const size_t total = (4096 + sz_desc + sz_stats + 65535) / 65536 * 65536;
         HIP_TRY(c->h_arena.alloc(total));
         char *p = (char *)c->h_arena.get();
         c->h_result = (unsigned long long *)p;
         c->h_result[0] = c->h_result[1] = c->h_result[2] = 0;
         p += 4096;
-        c->h_desc = (nps_row_desc *)p;
+        c->gt.h_desc = (nps_row_desc *)p;
         p += sz_desc;
-        c->h_stats = (nps_locus_stat *)p;
-        p += sz_stats;
-        for (int k = 0; k < nps_ctx::kRawSlots; ++k) {
-            c->h_raw[k] = (int32_t *)p;
-            p += sz_raw;
-        }
+        c->gt.h_stats = (nps_locus_stat *)p;
     }
-    HIP_TRY(c->d_lut.alloc(4ull * c->batch_cap));
-    HIP_TRY(c->d_stats.alloc(c->batch_cap));
-    for (int k = 0; k < nps_ctx::kRawSlots; ++k) HIP_TRY(c->ev_raw[k].create(hipEventDisableTiming));
+    // a slot holds the widest diploid record: two int32 per sample
+    HIP_TRY(c->raw.ensure(sizeof(int32_t) * 2 * std::max<uint64_t>(c->n, 1), c->stream.get()));
+    HIP_TRY(c->d_lut.alloc(4ull * c->gt.cap));
+    HIP_TRY(c->d_stats.alloc(c->gt.cap));
     HIP_TRY(c->d_part.alloc(c->n_chunks * c->geom.part_chunk_stride));
     HIP_TRY(c->d_scores.alloc(std::max<uint64_t>(c->n, 1)));
     HIP_TRY(c->d_nloci.alloc(256 / sizeof(unsigned long long)));
     HIP_TRY(c->d_timeout.alloc(256 / sizeof(unsigned int)));
     HIP_TRY(hipMemsetAsync(c->d_timeout.get(), 0, 256, c->stream.get()));
-    HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->batch_cap, c->stream.get()));
+    HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->gt.cap, c->stream.get()));
     rc = zero_state(c);
     if (rc) return rc;
     *out = owner.release();
@@ -507,16 +494,16 @@ static int run_batch(nps_ctx *c) {
         int rc = materialize_resident_stats(c);
         if (rc) return rc;
     }
-    if (c->batch_rows == 0 && c->ds_rows == 0) {
+    if (c->gt.rows == 0 && c->ds.rows == 0) {
         // only host rows pending: move them to ready
         for (auto &p : c->pending) c->ready.push_back(p.host);
         c->pending.clear();
         return NPS_OK;
     }
-    const uint32_t rows = c->batch_rows;
+    const uint32_t rows = c->gt.rows;
     if (rows) {
         const uint32_t rows_pad = (rows + 3) / 4 * 4;
-        HIP_TRY(hipMemcpyAsync(c->d_desc.get(), c->h_desc, sizeof(nps_row_desc) * rows,
+        HIP_TRY(hipMemcpyAsync(c->d_desc.get(), c->gt.h_desc, sizeof(nps_row_desc) * rows,
                                hipMemcpyHostToDevice, c->stream.get()));
         {
             ProfScope ps(c, P_PARAMS);
@@ -530,13 +517,13 @@ static int run_batch(nps_ctx *c) {
             HIP_TRY(launch_accumulate(c->stream.get(), c->d_codes.get(), c->stride_words, rows, c->d_lut.get(), c->geom,
                                       c->d_part.get()));
         }
-        HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats.get(), sizeof(nps_locus_stat) * rows,
+        HIP_TRY(hipMemcpyAsync(c->gt.h_stats, c->d_stats.get(), sizeof(nps_locus_stat) * rows,
                                hipMemcpyDeviceToHost, c->stream.get()));
         HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * rows, c->stream.get()));
     }
-    const uint32_t drows = c->ds_rows;
+    const uint32_t drows = c->ds.rows;
     if (drows) {
-        HIP_TRY(hipMemcpyAsync(c->d_ds_desc.get(), c->h_ds_desc, sizeof(nps_row_desc) * drows,
+        HIP_TRY(hipMemcpyAsync(c->d_ds_desc.get(), c->ds.h_desc, sizeof(nps_row_desc) * drows,
                                hipMemcpyHostToDevice, c->stream.get()));
         {
             ProfScope ps(c, P_TALLY);
@@ -555,40 +542,76 @@ static int run_batch(nps_ctx *c) {
             HIP_TRY(launch_ds_accumulate(c->stream.get(), c->d_ds.get(), c->ds_stride_f, c->n, c->d_ds_rowp.get(), drows,
                                          c->d_part.get(), c->n_chunks, c->geom.part_chunk_stride));
         }
-        HIP_TRY(hipMemcpyAsync(c->h_ds_stats, c->d_ds_stats.get(), sizeof(nps_locus_stat) * drows,
+        HIP_TRY(hipMemcpyAsync(c->ds.h_stats, c->d_ds_stats.get(), sizeof(nps_locus_stat) * drows,
                                hipMemcpyDeviceToHost, c->stream.get()));
     }
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     for (auto &p : c->pending)
-        c->ready.push_back(p.batch_idx < 0 ? p.host
-                                           : (p.is_ds ? c->h_ds_stats[p.batch_idx] : c->h_stats[p.batch_idx]));
+        c->ready.push_back(p.batch_idx < 0 ? p.host : (p.is_ds ? c->ds : c->gt).h_stats[p.batch_idx]);
     c->pending.clear();
-    c->batch_rows = 0;
-    c->ds_rows = 0;
+    c->gt.rows = 0;
+    c->ds.rows = 0;
     return NPS_OK;
 }
 
-static int begin_data_row(nps_ctx *c, int ref_is_effect, double beta, double eaf, uint32_t *slot) {
-    if (c->batch_rows == c->batch_cap) {
+// open the next row of batch `b` (run the batches first when it is full) and fill in its descriptor; row_flags: bits of
+// nps_row_desc::ref_is_effect above bit 0
+static int begin_data_row(nps_ctx *c, OpenBatch &b, int ref_is_effect, int row_flags, double beta, double eaf,
+                          uint32_t *slot) {
+    if (b.rows == b.cap) {
         int rc = run_batch(c);
         if (rc) return rc;
     }
-    *slot = c->batch_rows;
-    nps_row_desc &d = c->h_desc[*slot];
+    *slot = b.rows;
+    nps_row_desc &d = b.h_desc[*slot];
     d.beta = beta;
     d.eaf = eaf;
     d.kind = NPS_ROW_PRESENT;
-    d.ref_is_effect = ref_is_effect ? 1 : 0;
+    d.ref_is_effect = (ref_is_effect ? 1 : 0) | row_flags;
     return NPS_OK;
 }
 
-static void commit_data_row(nps_ctx *c, uint32_t slot) {
+static void commit_data_row(nps_ctx *c, OpenBatch &b, uint32_t slot) {
     PendingRow p;
     p.batch_idx = (int32_t)slot;
-    p.is_ds = 0;
+    p.is_ds = &b == &c->ds;
     memset(&p.host, 0, sizeof p.host);
     c->pending.push_back(p);
-    c->batch_rows = slot + 1;
+    b.rows = slot + 1;
+}
+
+// One row through a staging ring.  The caller may reuse its buffer on return, so `fill` copies it into the next pinned
+// slot; `queue` queues on `st` the work that reads the slot where it lies (a kernel, over PCIe: one launch per row instead
+// of a DMA copy and a launch that wait for each other, ~50 us per row); the slot's event goes behind it.  No stream
+// synchronisation per row; if `queue` fails no event is recorded.
+template <class Fill, class Queue>
+static int stage_row(StagingRing &ring, hipStream_t st, Fill fill, Queue queue) {
+    void *slot = nullptr;
+    HIP_TRY(ring.acquire(&slot));
+    fill(slot);
+    int rc = queue(slot);
+    if (rc) return rc;
+    HIP_TRY(ring.release(st));
+    return NPS_OK;
+}
+
+// a .bed / .pgen row of n samples into a slot: ceil(n/4) bytes, zero up to the word boundary
+static void stage_bed_row(void *slot, const uint8_t *bed_row, uint64_t n) {
+    const size_t bytes = (size_t)((n + 3) / 4), padded = sizeof(uint32_t) * words_for(n);
+    memcpy(slot, bed_row, bytes);
+    memset((char *)slot + bytes, 0, padded - bytes);
+}
+
+// the typed GT vector of a record; max_ploidy: what the destination holds
+static int check_raw_gt(int elem_bytes, int ploidy, int eaidx, int max_ploidy) {
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
+        return fail(NPS_E_INVAL, "elem_bytes %d (1, 2 or 4)", elem_bytes);
+    if (ploidy < 1) return fail(NPS_E_INVAL, "ploidy %d < 1", ploidy);
+    if (ploidy > max_ploidy)
+        return max_ploidy == 2 ? fail(NPS_E_UNSUPPORTED, "ploidy %d > 2 does not fit the 2-bit cohort", ploidy)
+                               : fail(NPS_E_UNSUPPORTED, "ploidy %d > 8", ploidy);
+    if (eaidx < 0) return fail(NPS_E_INVAL, "eaidx %d < 0 (nimpress.nim:380 doAssert)", eaidx);
+    return NPS_OK;
 }
 
 static int ensure_ds(nps_ctx *c);
@@ -600,47 +623,23 @@ static int push_gt_polyploid(nps_ctx *c, const void *gts, int elem_bytes, int pl
                              int ref_is_effect, double beta, double eaf) {
     int rc = ensure_ds(c);
     if (rc) return rc;
-    if (c->ds_rows == c->ds_cap) {
-        rc = run_batch(c);
-        if (rc) return rc;
-    }
-    const uint32_t slot = c->ds_rows;
-    nps_row_desc &d = c->h_ds_desc[slot];
-    d.beta = beta;
-    d.eaf = eaf;
-    d.kind = NPS_ROW_PRESENT;
     // the decoded row already counts the effect allele: flag bit 1 tells the DS kernels not to apply
     // the 2 - DS transform, bit 0 still selects the homref imputation value (nim:435-438)
-    d.ref_is_effect = (ref_is_effect ? 1 : 0) | 2;
+    uint32_t slot;
+    rc = begin_data_row(c, c->ds, ref_is_effect, 2, beta, eaf, &slot);
+    if (rc) return rc;
     if (c->n) {
         const size_t bytes = (size_t)elem_bytes * (size_t)ploidy * c->n;
-        if (bytes > c->h_poly[1].cap()) {  // the staging grows to the widest record seen (rare: once per context)
-            HIP_TRY(hipStreamSynchronize(c->stream.get()));
-            for (int k = 0; k < 2; ++k) {
-                c->h_poly[k].reset();
-                if (!c->ev_poly[k].get()) HIP_TRY(c->ev_poly[k].create(hipEventDisableTiming));
-            }
-            for (int k = 0; k < 2; ++k) HIP_TRY(c->h_poly[k].alloc(bytes));  // ([1] last: its size is the ring's)
-        }
-        // as for diploid rows: the caller may reuse `gts` on return, so it is copied into a pinned ring
-        // slot first (which the decode kernel reads where it lies); no stream synchronisation per row
-        const int k = c->poly_next;
-        c->poly_next ^= 1;
-        HIP_TRY(hipEventSynchronize(c->ev_poly[k].get()));
-        memcpy(c->h_poly[k].get(), gts, bytes);
-        {
+        HIP_TRY(c->poly.ensure(bytes, c->stream.get()));  // (rare: once or twice per context)
+        rc = stage_row(c->poly, c->stream.get(), [&](void *s) { memcpy(s, gts, bytes); }, [&](void *s) -> int {
             ProfScope ps(c, P_DECODE);
-            HIP_TRY(launch_decode_gt_to_ds(c->stream.get(), c->h_poly[k].get(), elem_bytes, c->n, ploidy, eaidx,
+            HIP_TRY(launch_decode_gt_to_ds(c->stream.get(), s, elem_bytes, c->n, ploidy, eaidx,
                                            c->d_ds.get() + (uint64_t)slot * c->ds_stride_f));
-        }
-        HIP_TRY(hipEventRecord(c->ev_poly[k].get(), c->stream.get()));
+            return NPS_OK;
+        });
+        if (rc) return rc;
     }
-    PendingRow p;
-    p.batch_idx = (int32_t)slot;
-    p.is_ds = 1;
-    memset(&p.host, 0, sizeof p.host);
-    c->pending.push_back(p);
-    c->ds_rows = slot + 1;
+    commit_data_row(c, c->ds, slot);
     return NPS_OK;
 }
 
@@ -648,35 +647,25 @@ static int push_gt_typed(nps_ctx *c, const void *gts, int elem_bytes, int ploidy
                          int ref_is_effect, double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
     if (c->n && !gts) return fail(NPS_E_INVAL, "gts is NULL");
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
-        return fail(NPS_E_INVAL, "elem_bytes %d (1, 2 or 4)", elem_bytes);
-    if (ploidy < 1) return fail(NPS_E_INVAL, "ploidy %d < 1", ploidy);
-    if (ploidy > 8) return fail(NPS_E_UNSUPPORTED, "ploidy %d > 8", ploidy);
-    if (eaidx < 0) return fail(NPS_E_INVAL, "eaidx %d < 0 (nimpress.nim:380 doAssert)", eaidx);
+    if (int arc = check_raw_gt(elem_bytes, ploidy, eaidx, 8)) return arc;
     HIP_TRY(hipSetDevice(c->device));
     if (ploidy > 2)
         return push_gt_polyploid(c, gts, elem_bytes, ploidy, eaidx, ref_is_effect, beta, eaf);
     uint32_t slot;
-    int rc = begin_data_row(c, ref_is_effect, beta, eaf, &slot);
+    int rc = begin_data_row(c, c->gt, ref_is_effect, 0, beta, eaf, &slot);
     if (rc) return rc;
     if (c->n) {
-        // the caller may reuse `gts` on return: copy it into a pinned ring slot first
-        const int k = c->raw_next;
-        c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
         const size_t bytes = (size_t)elem_bytes * (size_t)ploidy * c->n;
-        memcpy(c->h_raw[k], gts, bytes);
-        // the decode kernel reads the pinned slot itself, over PCIe: one launch per row instead of a DMA
-        // copy and a launch that wait for each other (copy engine <-> compute queue, ~50 us per row)
-        {
+        rc = stage_row(c->raw, c->stream.get(), [&](void *s) { memcpy(s, gts, bytes); }, [&](void *s) -> int {
             ProfScope ps(c, P_DECODE);
-            HIP_TRY(launch_decode_gt(c->stream.get(), c->h_raw[k], elem_bytes, c->n, ploidy, eaidx,
+            HIP_TRY(launch_decode_gt(c->stream.get(), s, elem_bytes, c->n, ploidy, eaidx,
                                      c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4, slot & 3,
                                      c->d_tally.get() + slot));
-        }
-        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
+            return NPS_OK;
+        });
+        if (rc) return rc;
     }
-    commit_data_row(c, slot);
+    commit_data_row(c, c->gt, slot);
     return NPS_OK;
 }
 
@@ -690,29 +679,39 @@ extern "C" int nps_push_gt_raw(nps_ctx *c, const void *gt, int elem_bytes, int p
     return push_gt_typed(c, gt, elem_bytes, ploidy, eaidx, ref_is_effect, beta, eaf);
 }
 
+// a row of 2-bit codes, arguments checked: bed_mode -1 = ceil(n/16) words of native codes, else ceil(n/4) bytes of a
+// .bed / .pgen row under that code map
+static int push_2bit(nps_ctx *c, const void *row, int bed_mode, int ref_is_effect, double beta, double eaf) {
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t slot;
+    int rc = begin_data_row(c, c->gt, ref_is_effect, 0, beta, eaf, &slot);
+    if (rc) return rc;
+    if (c->n) {
+        rc = stage_row(c->raw, c->stream.get(),
+                       [&](void *s) {
+                           if (bed_mode < 0)
+                               memcpy(s, row, sizeof(uint32_t) * c->n_words);
+                           else
+                               stage_bed_row(s, (const uint8_t *)row, c->n);
+                       },
+                       [&](void *s) -> int {
+                           ProfScope ps(c, P_TALLY);
+                           HIP_TRY(launch_tally_scatter_row(c->stream.get(), (const uint32_t *)s, c->n, bed_mode,
+                                                            c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4,
+                                                            slot & 3, c->d_tally.get() + slot));
+                           return NPS_OK;
+                       });
+        if (rc) return rc;
+    }
+    commit_data_row(c, c->gt, slot);
+    return NPS_OK;
+}
+
 extern "C" int nps_push_packed(nps_ctx *c, const uint32_t *row, int ref_is_effect, double beta,
                                double eaf) {
     if (int urc = check_usable(c)) return urc;
     if (c->n && !row) return fail(NPS_E_INVAL, "row is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    uint32_t slot;
-    int rc = begin_data_row(c, ref_is_effect, beta, eaf, &slot);
-    if (rc) return rc;
-    if (c->n) {
-        const int k = c->raw_next;
-        c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
-        memcpy(c->h_raw[k], row, sizeof(uint32_t) * c->n_words);
-        {
-            ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_scatter_row(c->stream.get(), reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n, -1,
-                                             c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4,
-                                             slot & 3, c->d_tally.get() + slot));
-        }
-        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
-    }
-    commit_data_row(c, slot);
-    return NPS_OK;
+    return push_2bit(c, row, -1, ref_is_effect, beta, eaf);
 }
 
 extern "C" int nps_push_bed(nps_ctx *c, const uint8_t *bed_row, int effect_is_a1, int ref_is_effect,
@@ -720,38 +719,18 @@ extern "C" int nps_push_bed(nps_ctx *c, const uint8_t *bed_row, int effect_is_a1
     if (int urc = check_usable(c)) return urc;
     if (c->n && !bed_row) return fail(NPS_E_INVAL, "bed_row is NULL");
     if (effect_is_a1 < 0 || effect_is_a1 > NPS_MAP_PGEN_REF) return fail(NPS_E_INVAL, "bad code map %d", effect_is_a1);
-    HIP_TRY(hipSetDevice(c->device));
-    uint32_t slot;
-    int rc = begin_data_row(c, ref_is_effect, beta, eaf, &slot);
-    if (rc) return rc;
-    if (c->n) {
-        const int k = c->raw_next;
-        c->raw_next = (k + 1) % nps_ctx::kRawSlots;
-        HIP_TRY(hipEventSynchronize(c->ev_raw[k].get()));
-        const size_t bytes = (size_t)((c->n + 3) / 4), padded = sizeof(uint32_t) * c->n_words;
-        memcpy(c->h_raw[k], bed_row, bytes);
-        memset((char *)c->h_raw[k] + bytes, 0, padded - bytes);
-        {
-            ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_tally_scatter_row(c->stream.get(), reinterpret_cast<const uint32_t *>(c->h_raw[k]), c->n,
-                                             effect_is_a1,
-                                             c->d_codes.get() + (uint64_t)(slot >> 2) * c->stride_words * 4,
-                                             slot & 3, c->d_tally.get() + slot));
-        }
-        HIP_TRY(hipEventRecord(c->ev_raw[k].get(), c->stream.get()));
-    }
-    commit_data_row(c, slot);
-    return NPS_OK;
+    return push_2bit(c, bed_row, effect_is_a1, ref_is_effect, beta, eaf);
 }
 
-// lazily allocate the DS streaming batch
+// lazily allocate the DS streaming batch.  The ring is built last and is empty after any failure of its own, so a
+// built ring says that everything before it succeeded; a call that failed half-way is repeated from the start.
 static int ensure_ds(nps_ctx *c) {
-    if (c->ev_ds_raw[1].get()) return NPS_OK;  // (created last: the batch is complete)
+    if (c->ds_raw.built()) return NPS_OK;
     c->ds_stride_f = ds_stride_floats(c->n);
     const uint64_t row_bytes = c->ds_stride_f * 4;
     uint64_t cap = (64ull << 20) / row_bytes;
     cap = std::max<uint64_t>(4, std::min<uint64_t>(cap, 1024));
-    c->ds_cap = (uint32_t)cap;
+    c->ds.cap = (uint32_t)cap;
     HIP_TRY(c->d_ds.alloc(c->ds_stride_f * cap));
     HIP_TRY(hipMemsetAsync(c->d_ds.get(), 0, row_bytes * cap, c->stream.get()));
     HIP_TRY(c->d_ds_desc.alloc(cap));
@@ -760,19 +739,10 @@ static int ensure_ds(nps_ctx *c) {
     HIP_TRY(c->d_ds_stats.alloc(cap));
     auto up = [](size_t v) { return (v + 4095) / 4096 * 4096; };
     const size_t sz_desc = up(sizeof(nps_row_desc) * cap), sz_stats = up(sizeof(nps_locus_stat) * cap);
-    const size_t sz_raw = up(sizeof(float) * std::max<uint64_t>(c->n, 1));
-    size_t total = (sz_desc + sz_stats + 2 * sz_raw + 65535) / 65536 * 65536;
-    HIP_TRY(c->h_ds_arena.alloc(total));
-    char *p = (char *)c->h_ds_arena.get();
-    c->h_ds_desc = (nps_row_desc *)p;
-    p += sz_desc;
-    c->h_ds_stats = (nps_locus_stat *)p;
-    p += sz_stats;
-    for (int k = 0; k < 2; ++k) {
-        c->h_ds_raw[k] = (float *)p;
-        p += sz_raw;
-        if (!c->ev_ds_raw[k].get()) HIP_TRY(c->ev_ds_raw[k].create(hipEventDisableTiming));
-    }
+    HIP_TRY(c->h_ds_arena.alloc((sz_desc + sz_stats + 65535) / 65536 * 65536));
+    c->ds.h_desc = (nps_row_desc *)c->h_ds_arena.get();
+    c->ds.h_stats = (nps_locus_stat *)((char *)c->h_ds_arena.get() + sz_desc);
+    HIP_TRY(c->ds_raw.ensure(sizeof(float) * std::max<uint64_t>(c->n, 1), c->stream.get()));
     return NPS_OK;
 }
 
@@ -782,31 +752,18 @@ extern "C" int nps_push_ds(nps_ctx *c, const float *ds, int ref_is_effect, doubl
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_ds(c);
     if (rc) return rc;
-    if (c->ds_rows == c->ds_cap) {
-        rc = run_batch(c);
+    uint32_t slot;
+    rc = begin_data_row(c, c->ds, ref_is_effect, 0, beta, eaf, &slot);
+    if (rc) return rc;
+    if (c->n) {
+        rc = stage_row(c->ds_raw, c->stream.get(), [&](void *s) { memcpy(s, ds, sizeof(float) * c->n); }, [&](void *s) -> int {
+            HIP_TRY(hipMemcpyAsync(c->d_ds.get() + (uint64_t)slot * c->ds_stride_f, s, sizeof(float) * c->n,
+                                   hipMemcpyHostToDevice, c->stream.get()));
+            return NPS_OK;
+        });
         if (rc) return rc;
     }
-    const uint32_t slot = c->ds_rows;
-    nps_row_desc &d = c->h_ds_desc[slot];
-    d.beta = beta;
-    d.eaf = eaf;
-    d.kind = NPS_ROW_PRESENT;
-    d.ref_is_effect = ref_is_effect ? 1 : 0;
-    if (c->n) {
-        const int k = c->ds_raw_next;
-        c->ds_raw_next = (k + 1) % 2;
-        HIP_TRY(hipEventSynchronize(c->ev_ds_raw[k].get()));
-        memcpy(c->h_ds_raw[k], ds, sizeof(float) * c->n);
-        HIP_TRY(hipMemcpyAsync(c->d_ds.get() + (uint64_t)slot * c->ds_stride_f, c->h_ds_raw[k],
-                               sizeof(float) * c->n, hipMemcpyHostToDevice, c->stream.get()));
-        HIP_TRY(hipEventRecord(c->ev_ds_raw[k].get(), c->stream.get()));
-    }
-    PendingRow p;
-    p.batch_idx = (int32_t)slot;
-    p.is_ds = 1;
-    memset(&p.host, 0, sizeof p.host);
-    c->pending.push_back(p);
-    c->ds_rows = slot + 1;
+    commit_data_row(c, c->ds, slot);
     return NPS_OK;
 }
 
@@ -1155,7 +1112,7 @@ extern "C" int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrow
 
 // one row of a NPS_FMT_GT2 cohort from the buffer a VCF/BCF record holds, decoded on the device (the resident form of
 // nps_push_gt_raw / nps_push_bed: same kernels, the cohort is the destination)
-static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes, int *slot) {
+static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes) {
     if (!c) return fail(NPS_E_INVAL, "cohort is NULL");
     if (c->format != NPS_FMT_GT2) return fail(NPS_E_UNSUPPORTED, "rows are pushed into NPS_FMT_GT2 cohorts only");
     if (row >= c->n_rows) return fail(NPS_E_INVAL, "row %llu outside cohort of %llu rows", (unsigned long long)row,
@@ -1167,64 +1124,46 @@ static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes, int *s
         if (rc) return rc;
         HIP_TRY(c->push_stream.create());
     }
-    if (!c->ev_push[1].get()) {  // (with the stream, on the first push)
-        HIP_TRY(c->d_push_tally.alloc(256 / sizeof(unsigned long long)));
-        for (int k = 0; k < 2; ++k)
-            if (!c->ev_push[k].get()) HIP_TRY(c->ev_push[k].create(hipEventDisableTiming));
-    }
+    if (!c->d_push_tally.get()) HIP_TRY(c->d_push_tally.alloc(256 / sizeof(unsigned long long)));
     if (c->optimized) {
         HIP_TRY(hipDeviceSynchronize());
         int rc = cohort_unoptimize(c);
         if (rc) return rc;
     }
-    if (bytes > c->h_push[1].cap()) {
-        HIP_TRY(hipStreamSynchronize(c->push_stream.get()));
-        for (int k = 0; k < 2; ++k) c->h_push[k].reset();
-        for (int k = 0; k < 2; ++k) HIP_TRY(c->h_push[k].alloc(bytes));  // ([1] last: its size is the ring's)
-    }
-    *slot = c->push_next;
-    c->push_next ^= 1;
-    HIP_TRY(hipEventSynchronize(c->ev_push[*slot].get()));
+    HIP_TRY(c->push.ensure(bytes, c->push_stream.get()));
     return NPS_OK;
 }
 
 extern "C" int nps_cohort_push_gt_raw(nps_cohort *c, uint64_t row, const void *gt, int elem_bytes, int ploidy,
                                       int eaidx) {
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
-        return fail(NPS_E_INVAL, "elem_bytes %d (1, 2 or 4)", elem_bytes);
-    if (ploidy < 1) return fail(NPS_E_INVAL, "ploidy %d < 1", ploidy);
-    if (ploidy > 2) return fail(NPS_E_UNSUPPORTED, "ploidy %d > 2 does not fit the 2-bit cohort", ploidy);
-    if (eaidx < 0) return fail(NPS_E_INVAL, "eaidx %d < 0 (nimpress.nim:380 doAssert)", eaidx);
+    if (int arc = check_raw_gt(elem_bytes, ploidy, eaidx, 2)) return arc;
     if (c && c->n_samples && !gt) return fail(NPS_E_INVAL, "gt is NULL");
     const size_t bytes = c ? (size_t)elem_bytes * (size_t)ploidy * c->n_samples : 0;
-    int k = 0;
-    int rc = cohort_push_prepare(c, row, std::max<size_t>(bytes, 16), &k);
+    int rc = cohort_push_prepare(c, row, std::max<size_t>(bytes, 16));
     if (rc) return rc;
     if (c->n_samples == 0) return NPS_OK;
-    memcpy(c->h_push[k].get(), gt, bytes);
     const uint64_t sw = c->stride_bytes / 4;
-    HIP_TRY(launch_decode_gt(c->push_stream.get(), c->h_push[k].get(), elem_bytes, c->n_samples, ploidy, eaidx,
-                             (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3), c->d_push_tally.get()));
-    HIP_TRY(hipEventRecord(c->ev_push[k].get(), c->push_stream.get()));
-    return NPS_OK;
+    return stage_row(c->push, c->push_stream.get(), [&](void *s) { memcpy(s, gt, bytes); }, [&](void *s) -> int {
+        HIP_TRY(launch_decode_gt(c->push_stream.get(), s, elem_bytes, c->n_samples, ploidy, eaidx,
+                                 (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3), c->d_push_tally.get()));
+        return NPS_OK;
+    });
 }
 
 extern "C" int nps_cohort_push_bed(nps_cohort *c, uint64_t row, const uint8_t *bed_row, int effect_is_a1) {
     if (c && c->n_samples && !bed_row) return fail(NPS_E_INVAL, "bed_row is NULL");
     if (effect_is_a1 < 0 || effect_is_a1 > NPS_MAP_PGEN_REF) return fail(NPS_E_INVAL, "bad code map %d", effect_is_a1);
     const size_t bytes = c ? (size_t)((c->n_samples + 3) / 4) : 0;
-    int k = 0;
-    int rc = cohort_push_prepare(c, row, std::max<size_t>((bytes + 3) / 4 * 4 + 16, 16), &k);
+    int rc = cohort_push_prepare(c, row, (bytes + 3) / 4 * 4 + 16);
     if (rc) return rc;
     if (c->n_samples == 0) return NPS_OK;
-    memset(c->h_push[k].get(), 0, (bytes + 3) / 4 * 4 + 16);
-    memcpy(c->h_push[k].get(), bed_row, bytes);
     const uint64_t sw = c->stride_bytes / 4;
-    HIP_TRY(launch_tally_scatter_row(c->push_stream.get(), reinterpret_cast<const uint32_t *>(c->h_push[k].get()), c->n_samples,
-                                     effect_is_a1, (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3),
-                                     c->d_push_tally.get()));
-    HIP_TRY(hipEventRecord(c->ev_push[k].get(), c->push_stream.get()));
-    return NPS_OK;
+    return stage_row(c->push, c->push_stream.get(), [&](void *s) { stage_bed_row(s, bed_row, c->n_samples); }, [&](void *s) -> int {
+        HIP_TRY(launch_tally_scatter_row(c->push_stream.get(), (const uint32_t *)s, c->n_samples, effect_is_a1,
+                                         (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3),
+                                         c->d_push_tally.get()));
+        return NPS_OK;
+    });
 }
 
 // NPS_FMT_DS16 <-> float32 rows of the host, through a float32 staging buffer of at most 256 MiB.  Upload: a row that holds
