@@ -985,6 +985,7 @@ static int gt2_transfer(const nps_cohort *c, uint64_t row0, uint64_t nrows, void
     if (row0 & 3) return fail(NPS_E_INVAL, "row0 must be a multiple of 4 for 2-bit cohorts");
     const uint64_t chunk_groups = std::max<uint64_t>(1, (64ull << 20) / (sw * 16));
     std::vector<uint32_t> buf;
+    // (more than one chunk: tests/test_gpu_seams.py seam_tall_row_upload_and_download_cross_their_chunks)
     for (uint64_t r = 0; r < nrows; r += chunk_groups * 4) {
         const uint64_t k = std::min<uint64_t>(chunk_groups * 4, nrows - r);  // rows in this chunk
         const uint64_t groups = (k + 3) / 4;
@@ -1013,6 +1014,18 @@ static int gt2_transfer(const nps_cohort *c, uint64_t row0, uint64_t nrows, void
     return NPS_OK;
 }
 
+// k host rows of `width` bytes -> staging rows `pitch` bytes apart.  Short rows whose width or stride is no multiple of 4
+// (.bed / .pgen rows of a few dozen samples) cost hipMemcpy2D microseconds EACH (a minute for eight million rows): those are
+// laid out at the pitch on the host, padding zero, and go over in one copy.
+static hipError_t stage_host_rows(void *d_stage, size_t pitch, const char *host, size_t host_stride, size_t width, uint64_t k,
+                                  std::vector<char> &repitched) {
+    if (((width | host_stride) & 3) == 0 || pitch > 4096)
+        return hipMemcpy2D(d_stage, pitch, host, host_stride, width, k, hipMemcpyHostToDevice);
+    repitched.assign(k * pitch, 0);
+    for (uint64_t j = 0; j < k; ++j) memcpy(repitched.data() + j * pitch, host + j * host_stride, width);
+    return hipMemcpy(d_stage, repitched.data(), k * pitch, hipMemcpyHostToDevice);
+}
+
 // rows of a host buffer -> staging on the device -> interleave (and, for .bed rows, recode) kernel.
 // width = bytes of one source row; bed_mode: nullptr (native codes) or per-row effect-is-A1 flags.
 static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *host_rows,
@@ -1027,11 +1040,13 @@ static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *
     DevBuf<uint8_t> d_mode;
     HIP_TRY(d_stage.alloc(chunk * src_stride_words));
     if (bed_mode) HIP_TRY(d_mode.alloc(chunk));
+    std::vector<char> repitched;
+    // (more than one chunk: tests/test_gpu_seams.py seam_tall_row_upload_*, seam_wide_row_layout_upload_and_download)
     for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
         HIP_TRY(hipMemsetAsync(d_stage.get(), 0, chunk * src_stride_words * 4, nullptr));
-        HIP_TRY(hipMemcpy2D(d_stage.get(), src_stride_words * 4, (const char *)host_rows + r * host_stride,
-                            host_stride, width, k, hipMemcpyHostToDevice));
+        HIP_TRY(stage_host_rows(d_stage.get(), src_stride_words * 4, (const char *)host_rows + r * host_stride, host_stride,
+                                width, k, repitched));
         if (bed_mode) HIP_TRY(hipMemcpy(d_mode.get(), bed_mode + r, k, hipMemcpyHostToDevice));
         HIP_TRY(launch_interleave_rows(nullptr, d_stage.get(), src_stride_words, k, c->n_samples, d_mode.get(),
                                        (uint32_t *)(c->d_data.get() + ((row0 + r) >> 2) * sw * 16), sw));
@@ -1043,9 +1058,11 @@ static int gt2_upload(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *
 // NPS_FMT_GT2X: units -> plain rows (C-ABI order and codes), through a device staging buffer of whole superblocks
 static int gt2x_download(const nps_cohort *c, uint64_t row0, uint64_t nrows, void *host_rows, size_t host_stride) {
     const uint64_t n_words = words_for(c->n_samples), sw = (n_words + 3) / 4 * 4;
-    const uint64_t chunk = std::max<uint64_t>(128, (256ull << 20) / (sw * 4) / 128 * 128);
+    uint64_t chunk = std::max<uint64_t>(128, (256ull << 20) / (sw * 4) / 128 * 128);
+    chunk = std::min<uint64_t>(chunk, 128ull * 65535);  // one launch_gt2x_to_rows takes 65 535 superblocks
     DevBuf<uint32_t> d_stage;
     HIP_TRY(d_stage.alloc(std::min(chunk, (nrows + 127) / 128 * 128) * sw));
+    // (more than one chunk: tests/test_gpu_seams.py seam_tall_strip_upload_in_one_call, seam_wide_strip_layout_fill_and_download)
     for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
         HIP_TRY(launch_gt2x_to_rows(nullptr, c->d_data.get(), c->n_samples, c->n_rows, row0 + r, k, d_stage.get(), sw));
@@ -1074,11 +1091,13 @@ static int gt2x_fill(nps_cohort *c, uint64_t row0, uint64_t nrows, const void *h
     DevBuf<uint8_t> d_map;
     HIP_TRY(d_stage.alloc(std::min(chunk, n_sb * 128) * sw));
     if (code_map) HIP_TRY(d_map.alloc(std::min(chunk, nrows)));
+    std::vector<char> repitched;
     HIP_TRY(hipMemsetAsync(c->d_mx_row_tally.get() + sb0 * 128, 0, sizeof(unsigned long long) * n_sb * 128, nullptr));
+    // (more than one chunk: tests/test_gpu_seams.py seam_tall_strip_upload*_in_one_call, seam_wide_strip_layout_fill_and_download)
     for (uint64_t r = 0; r < nrows; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
-        HIP_TRY(hipMemcpy2D(d_stage.get(), sw * 4, (const char *)host_rows + r * host_stride, host_stride, width, k,
-                            hipMemcpyHostToDevice));
+        HIP_TRY(stage_host_rows(d_stage.get(), sw * 4, (const char *)host_rows + r * host_stride, host_stride, width, k,
+                                repitched));
         if (code_map) HIP_TRY(hipMemcpy(d_map.get(), code_map + r, k, hipMemcpyHostToDevice));
         HIP_TRY(launch_fill_gt2x_rows(nullptr, d_stage.get(), sw, d_map.get(), c->n_samples, c->n_rows, row0 + r, k,
                                       c->d_data.get(), c->d_mx_row_tally.get()));
@@ -1178,6 +1197,7 @@ static int ds16_transfer(nps_cohort *c, uint64_t row0, uint64_t nrows, void *hos
     HIP_TRY(d_bad.alloc(chunk));
     std::vector<unsigned char> bad(chunk);
     long long first_bad = -1;
+    // (more than one chunk: tests/test_gpu_seams.py seam_ds16_staging_chunks_and_the_row_an_error_names)
     for (uint64_t r = 0; r < nrows && first_bad < 0; r += chunk) {
         const uint64_t k = std::min(chunk, nrows - r);
         uint16_t *rows = (uint16_t *)c->d_data.get() + (row0 + r) * stride_e;
@@ -1522,6 +1542,7 @@ static int mx_special_pass(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row
     int rc = ensure_all_chunks(c);
     if (rc) return rc;
     ProfScope ps(c, P_ACCUM);
+    // (more than one batch: tests/test_gpu_seams.py seam_special_rows_in_two_batches)
     for (uint64_t b0 = 0; b0 < K; b0 += B) {
         const uint64_t k = std::min(B, K - b0), k_pad = (k + 3) / 4 * 4;
         for (uint64_t j = b0; j < b0 + k;) {  // one launch per run of consecutive rows
@@ -1735,6 +1756,7 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
     int rc = ensure_all_chunks(c);
     if (rc) return rc;
     guard.armed = true;
+    // (more than one block: tests/test_gpu_seams.py seam_ds32_two_pass_blocks)
     for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
         const uint64_t k = std::min(block_rows, m - r0);
         {
@@ -1795,6 +1817,7 @@ static int score_run_gt2(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint
     if (rc) return rc;
     guard.armed = true;
     c->rtally_clean = false;  // the two-pass tally kernel leaves its counts in d_rtally
+    // (more than one block: tests/test_gpu_seams.py seam_tall_row_two_pass_blocks)
     for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
         const uint64_t k = std::min(block_rows, m - r0);
         const uint64_t k_pad = (k + 3) / 4 * 4;  // only the last block can be ragged

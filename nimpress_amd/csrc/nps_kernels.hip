@@ -336,6 +336,7 @@ hipError_t launch_cohort_parity(hipStream_t st, uint32_t *d_codes, uint64_t stri
     const uint64_t n_words = words_for(n_samples), n_groups = (n_rows + 3) / 4;
     if (n_groups == 0 || n_words == 0) return hipSuccess;
     (void)hipGetLastError();
+    // (more than one launch: tests/test_gpu_seams.py seam_tall_row_optimize_and_rewrite_cross_the_parity_launches)
     for (uint64_t g0 = 0; g0 < n_groups; g0 += 65535) {
         const uint64_t k = std::min<uint64_t>(65535, n_groups - g0);
         hipLaunchKernelGGL(cohort_parity_kernel, dim3((uint32_t)((n_words + 255) / 256), (uint32_t)k), dim3(256), 0,

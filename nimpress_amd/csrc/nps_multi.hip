@@ -241,6 +241,7 @@ hipError_t launch_convert_gt2m(hipStream_t st, const uint32_t *d_src, uint64_t s
     hipError_t e = hipMemsetAsync(d_tally, 0, sizeof(unsigned long long) * n_rows, st);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
+    // (more than one launch: tests/test_gpu_seams.py seam_tall_strip_conversions_cross_their_launches)
     for (uint64_t sb = 0; sb < n_sb; sb += 65535) {
         const uint64_t k = std::min<uint64_t>(65535, n_sb - sb);
         hipLaunchKernelGGL(convert_gt2m_kernel, dim3((uint32_t)((n_words + 31) / 32), (uint32_t)k), dim3(256), 0, st,

@@ -852,6 +852,7 @@ hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint
     if (!d_tally) return hipErrorInvalidValue;
     const MxGeom gm = mx_geom(n_samples, n_rows);
     (void)hipGetLastError();
+    // (more than one launch: tests/test_gpu_seams.py seam_tall_strip_conversions_cross_their_launches)
     for (uint64_t sb = 0; sb < gm.n_sb; sb += 32768) {
         const uint64_t k = std::min<uint64_t>(32768, gm.n_sb - sb);
         hipLaunchKernelGGL(fill_gt2x_kernel<kFillGt2>, dim3((gm.P + kFillStrips - 1) / kFillStrips, (uint32_t)k), dim3(256), 0, st,
