@@ -363,18 +363,34 @@ int nps_score_cohort_def(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0
 
 /* ---- several score definitions in ONE pass over a resident cohort --------------------------
  * The reference evaluates one score per run (nimpress.nim:634-641); S scores over the same cohort are S
- * passes over the genotypes.  Here the S definitions are applied together: scores[N x S] =
- * dosage[N x M] . weights[M x S] on the matrix cores (int8 codes x base-256 digits of the fixed-point
- * weights, exact integer accumulation: DESIGN.md), the genotypes are read once for all S.
+ * passes over the genotypes.  Here the S definitions are applied together, on either kind of cohort:
+ *
+ *   NPS_FMT_GT2M (2-bit genotypes): scores[N x S] = dosage[N x M] . weights[M x S] on the matrix cores (int8 codes x
+ *     base-256 digits of the fixed-point weights, exact integer accumulation: DESIGN.md); the genotypes are read once
+ *     for all S, the whole-row tallies come with the cohort.
+ *   NPS_FMT_DS32 / NPS_FMT_DS16 (dosages): two reads whatever S is -- one pass counts every row's tallies (nmissing, the
+ *     sum of DS and of 2 - DS: nps_multi_row_tallies), one accumulates all S scores, per sample and score the reference's
+ *     own float64 multiply and add, rows in order inside a row chunk (nps_multi_geometry), the chunks added in fixed order.
+ *     Measured on an MI355X (200 000 samples x 100 000 rows): the two reads beat S single-read passes
+ *     (nps_score_cohort_def) from S = 4 on for float32 dosages (S = 8: 48 ms against 102) and from S = 2 on for
+ *     NPS_FMT_DS16 (S = 8: 44 ms against 119); below that, score the definitions one by one.
  *
  * Position j of every definition refers to cohort row cohort_row0 + j (a cohort holding the union of
  * the scores' loci); per (score, position) `kind` says what that score does with the row:
  * NPS_ROW_PRESENT (the genotypes count), UNCOVERED / ABSENT / FILTERED (the host's early returns of
  * getImputedDosages, nimpress.nim:526-558: a constant, no genotypes) or NPS_ROW_NOT_IN_SCORE (the score
- * file does not list the locus).  Results per score are those of the single-score entry points
- * (same decisions, nloci bit-exact, scores within ~1e-13 relative: the weights are quantised to 2^-49 of
- * the largest one).  beta must be finite and eaf not infinite (NPS_E_UNSUPPORTED otherwise, naming the row; a NaN
- * eaf is scored). */
+ * file does not list the locus).  Results per score are those of the single-score entry points: same decisions, nloci
+ * bit-exact.  Scores of a 2-bit cohort are within ~1e-13 relative (the weights are quantised to 2^-49 of the largest
+ * one); scores of a dosage cohort carry the bound of the single-score DS paths -- plain float64: every term d x beta
+ * rounded once, the running sum once per row -- and any finite dosage is taken, not only [0, 2].  A definition's column
+ * of a dosage pass has the same bits whatever other definitions share the pass.  beta must be finite and eaf not
+ * infinite (NPS_E_UNSUPPORTED otherwise, naming the row; a NaN eaf is scored).
+ *
+ * ref_is_effect on a dosage cohort: 1 = the effect allele is REF, the dosage is 2 - DS (and the homref imputation
+ * value 2); with NPS_RIE_COUNTS_EFFECT set the row ALREADY counts the effect allele -- no 2 - DS -- and bit 0 alone
+ * selects the homref imputation value (a host that decodes GT records to dosage rows of the effect allele passes
+ * (ea == ref ? 1 : 0) | NPS_RIE_COUNTS_EFFECT). */
+#define NPS_RIE_COUNTS_EFFECT 2
 #define NPS_ROW_NOT_IN_SCORE 4
 #define NPS_MULTI_MAX_SCORES 8
 typedef struct nps_multi nps_multi;
@@ -402,9 +418,11 @@ int nps_multi_create(nps_multi **out, int device, uint64_t n_samples, const nps_
  * than 4 scores the pass needs up to a quarter fewer matrix instructions.  40: five leading digits, 2^-32 x B per missing
  * genotype, an eighth fewer matrix instructions with 7 or 8 scores (round 5; like 32 an option, not the default: a sample
  * whose terms cancel is not within 1e-6 of its own score over a million rows).  NaN imputation values
- * (imp-sample fail / int_fail below --mincs) are exact in both modes.  Applies to the following calls. */
+ * (imp-sample fail / int_fail below --mincs) are exact in both modes.  Applies to the following calls.  It has no
+ * meaning on a dosage cohort (float64 arithmetic, no fixed-point weights) and is ignored there. */
 int nps_multi_set_missing_weight_bits(nps_multi *m, int bits);
-/* cohort_row0 must be a multiple of 128; calls accumulate (chunks of a larger matrix) until nps_multi_reset.
+/* The cohort is NPS_FMT_GT2M, NPS_FMT_DS32 or NPS_FMT_DS16 (NPS_E_INVAL otherwise).  cohort_row0 must be a multiple of
+ * 128; calls accumulate (chunks of a larger matrix, also on cohorts of different formats) until nps_multi_reset.
  * Errors as for nps_score_cohort_def: refused calls leave the context unchanged; a HIP failure during the pass
  * makes every later call return NPS_E_STATE until nps_multi_reset. */
 int nps_score_cohort_multi(nps_multi *m, const nps_cohort *c, uint64_t cohort_row0, const nps_multidef *def);
@@ -425,8 +443,20 @@ int nps_multi_device(const nps_multi *m);
 int nps_multi_partial(nps_multi *m, double *sums_out, uint64_t *nloci_out);
 int nps_multi_reset(nps_multi *m, const nps_params *params /* NULL = keep */);
 void nps_multi_destroy(nps_multi *m);
-/* device time (HIP events) of the calls since the last reset: weight digits, the product, the fold */
+/* device time (HIP events) of the calls since the last reset: weight digits, the product, the fold -- on a dosage
+ * cohort: tally + params, the accumulation, the fold */
 int nps_multi_timing(nps_multi *m, double *ms_params, double *ms_product, double *ms_fold);
+/* The tallies of rows first .. first + n of the most recent nps_score_cohort_multi call, which must have been on a dosage
+ * cohort (indices relative to that call's cohort_row0): nmissing, the sum of DS and the sum of 2 - DS over the
+ * non-missing samples -- bit for bit the neffect nps_flush reports for the row pushed with nps_push_ds, ref_is_effect 0
+ * and 1.  Waits for the pass.  NPS_E_STATE when the last call was on a NPS_FMT_GT2M cohort or the context was reset
+ * since; NPS_E_INVAL when the range is out of bounds.  Any of the three outputs may be NULL. */
+int nps_multi_row_tallies(nps_multi *m, uint64_t first, uint64_t n, uint64_t *nmissing_out, double *sum_out,
+                          double *sum_flipped_out);
+/* The accumulation plan of a dosage format (NPS_FMT_DS32, NPS_FMT_DS16) for n_rows rows: row_chunks chunks of
+ * rows_per_chunk rows (the last one shorter), a function of the context's samples, n_rows and the chip -- never of the
+ * number of scores.  For tests that want to cross a chunk seam.  NPS_FMT_GT2M: NPS_E_UNSUPPORTED. */
+int nps_multi_geometry(const nps_multi *m, int format, uint64_t n_rows, uint32_t *row_chunks, uint32_t *rows_per_chunk);
 /* NPS_FMT_GT2 cohort (plain order) -> NPS_FMT_GT2M or NPS_FMT_GT2X cohort of the same shape, either with the whole-row
  * tallies of every row, counted from the tiles the conversion moves anyway */
 int nps_cohort_convert(nps_cohort *dst, const nps_cohort *src);

@@ -22,6 +22,7 @@ ROW_PRESENT, ROW_UNCOVERED, ROW_ABSENT, ROW_FILTERED = 0, 1, 2, 3
 REASON_GENOTYPED, REASON_UNCOVERED, REASON_ABSENT, REASON_FILTERED, REASON_MAXMIS = range(5)
 FMT_GT2, FMT_DS32, FMT_GT2M, FMT_GT2X, FMT_GT_AUTO, FMT_DS16 = 0, 1, 2, 3, 4, 5
 ROW_NOT_IN_SCORE = 4
+RIE_COUNTS_EFFECT = 2   # dosage cohorts: the row already counts the effect allele (NPS_RIE_COUNTS_EFFECT)
 MULTI_MAX_SCORES = 8
 MODE_AUTO, MODE_TWOPASS, MODE_FUSED = 0, 1, 2
 
@@ -64,7 +65,7 @@ SYMBOLS = [
     "nps_cohort_convert", "nps_cohort_row_tallies", "nps_cohort_keep_tallies", "nps_cohort_has_tallies", "nps_multi_set_missing_weight_bits",
     "nps_cohort_push_gt_raw", "nps_cohort_push_bed", "nps_multi_partial_device", "nps_multi_partial",
     "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes", "nps_cohort_rows_tallied",
-    "nps_live_resources",
+    "nps_live_resources", "nps_multi_row_tallies", "nps_multi_geometry",
 ]
 
 
@@ -200,6 +201,8 @@ def load(with_torch: bool = True):
     dp = C.POINTER(C.c_double)
     L.nps_multi_timing.argtypes = [vp, dp, dp, dp]
     L.nps_multi_set_missing_weight_bits.argtypes = [vp, i32]
+    L.nps_multi_row_tallies.argtypes = [vp, u64, u64, vp, vp, vp]
+    L.nps_multi_geometry.argtypes = [vp, i32, u64, u32p, u32p]
     L.nps_cohort_convert.argtypes = [vp, vp]
     L.nps_cohort_row_tallies.argtypes = [vp, u64, u64, vp, vp]
     L.nps_cohort_keep_tallies.argtypes = [vp]
@@ -534,11 +537,13 @@ class MultiDef:
 
 
 class MultiScorer:
-    """computePolygenicScores for S score definitions in one pass over a FMT_GT2M cohort (matrix cores)"""
+    """computePolygenicScores for S score definitions in one pass over a FMT_GT2M cohort (matrix cores), or in two reads
+    of a FMT_DS32 / FMT_DS16 cohort (float64 per sample and score)"""
 
     def __init__(self, n_samples: int, params: NpsParams, n_scores: int, device: int = 0):
         self._h = C.c_void_p()
         self.n, self.n_scores = int(n_samples), int(n_scores)
+        self._last_rows = 0   # rows of the most recent score_cohort call (row_tallies)
         _check(load().nps_multi_create(C.byref(self._h), device, self.n, C.byref(params), self.n_scores))
 
     def set_missing_weight_bits(self, bits: int):
@@ -548,6 +553,7 @@ class MultiScorer:
 
     def score_cohort(self, cohort: Cohort, mdef: MultiDef, cohort_row0: int = 0):
         _check(load().nps_score_cohort_multi(self._h, cohort._h, cohort_row0, mdef._h))
+        self._last_rows = mdef.n_desc
 
     def finish(self, offsets) -> Tuple[np.ndarray, np.ndarray]:
         off = np.ascontiguousarray(offsets, dtype=np.float64)
@@ -577,6 +583,22 @@ class MultiScorer:
         a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
         _check(load().nps_multi_timing(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def row_tallies(self, first: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(nmissing, sum of DS, sum of 2 - DS) per row of the most recent score_cohort call, which was on a dosage cohort
+        (nps_multi_row_tallies); n=None: every row from `first` on"""
+        if n is None:
+            n = max(self._last_rows - int(first), 0)
+        nm = np.zeros(max(n, 1), dtype=np.uint64)
+        sm, sf = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.float64)
+        _check(load().nps_multi_row_tallies(self._h, int(first), int(n), nm.ctypes.data, sm.ctypes.data, sf.ctypes.data))
+        return nm[:n], sm[:n], sf[:n]
+
+    def geometry(self, n_rows: int, fmt: int = FMT_DS32) -> Tuple[int, int]:
+        """(row chunks, rows per chunk) of the accumulation over n_rows rows of a dosage format (nps_multi_geometry)"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        _check(load().nps_multi_geometry(self._h, int(fmt), int(n_rows), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def close(self):
         if self._h:

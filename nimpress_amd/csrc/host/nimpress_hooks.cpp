@@ -399,7 +399,7 @@ static long nh_compute_multi_impl(const char *score_paths, const char *vcf_path,
                                   int imp_missing, int imp_sample, double maxmis, double afmisp, long mincs, int ignorefilt,
                                   int device, int shard, int n_shards, bool partial, double *scores_out, long cap,
                                   unsigned long long *nloci_out, double *offsets_out, char *log_out, long log_cap,
-                                  double *d_out = nullptr) {
+                                  double *d_out = nullptr, bool accept_ds = false) {
     try {
         RunInputs in;
         // (a shard of the rows reads only its own records: an indexed file is opened for window-by-window fetches,
@@ -418,7 +418,7 @@ static long nh_compute_multi_impl(const char *score_paths, const char *vcf_path,
         std::vector<uint64_t> nloci;
         computePolygenicScoresMulti(scores, ptrs, in.vcf, in.restrict, in.cov, (ImputeMethodLocus)imp_locus,
                                     (ImputeMethodMissing)imp_missing, (ImputeMethodSample)imp_sample, maxmis, afmisp, mincs,
-                                    ignorefilt != 0, logs, device, &nloci, shard, n_shards, partial, d_out);
+                                    ignorefilt != 0, logs, device, &nloci, shard, n_shards, partial, d_out, accept_ds);
         for (size_t s = 0; s < scores.size(); ++s) {
             for (size_t i = 0; i < scores[s].size() && (long)i < cap; ++i) scores_out[s * (size_t)cap + i] = scores[s][i];
             if (nloci_out) nloci_out[s] = nloci[s];
@@ -471,6 +471,35 @@ long nh_compute_multi_dev(const char *score_paths, const char *vcf_path, const c
     return nh_compute_multi_impl(score_paths, vcf_path, bed_path_or_null, imp_locus, imp_missing, imp_sample, maxmis, afmisp,
                                  mincs, ignorefilt, device, shard, n_shards, partial != 0, nullptr, 0, nloci_out, offsets_out,
                                  log_out, log_cap, (double *)d_out);
+}
+
+// The three hooks above in one, with a flags word: bit 0 (host.py: MULTI_ACCEPT_DS) = FORMAT/DS records are scored too
+// (computePolygenicScoresMulti's acceptDs).  d_out non-null: results stay on the device (scores_out and cap unused);
+// partial: the block's un-normalised sums.
+long nh_compute_multi_ex(const char *score_paths, const char *vcf_path, const char *bed_path_or_null, int imp_locus,
+                         int imp_missing, int imp_sample, double maxmis, double afmisp, long mincs, int ignorefilt, int device,
+                         int shard, int n_shards, int partial, unsigned flags, double *scores_out, long cap, void *d_out,
+                         unsigned long long *nloci_out, double *offsets_out, char *log_out, long log_cap) {
+    if (!d_out && !scores_out) {
+        g_nh_error = "nh_compute_multi_ex: scores_out and d_out are NULL";
+        return -1;
+    }
+    return nh_compute_multi_impl(score_paths, vcf_path, bed_path_or_null, imp_locus, imp_missing, imp_sample, maxmis, afmisp,
+                                 mincs, ignorefilt, device, shard, n_shards, partial != 0, d_out ? nullptr : scores_out,
+                                 d_out ? 0 : cap, nloci_out, offsets_out, log_out, log_cap, (double *)d_out, (flags & 1u) != 0);
+}
+
+// the host's decode of a FORMAT/GT vector (elem_bytes 1 / 2 / 4) and of .bed / .pgen codes into the float32 row of effect
+// allele counts the one-pass dosage route uploads (decodeGtDosage, decodeCodeDosage): n values written, -1 on bad arguments
+long nh_decode_gt_dosage(const void *gts, int elem_bytes, long n, int ploidy, int eaidx, float *out) {
+    if (!gts || !out || n < 0 || ploidy < 1 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)) return -1;
+    decodeGtDosage(gts, elem_bytes, (size_t)n, ploidy, eaidx, out);
+    return n;
+}
+long nh_decode_code_dosage(const unsigned char *codes, long n, int code_map, float *out) {
+    if (!codes || !out || n < 0 || code_map < 0 || code_map > 3) return -1;
+    decodeCodeDosage(codes, (size_t)n, code_map, out);
+    return n;
 }
 
 double nh_dbinom(long x, long n, double p) { return dbinom(x, n, p); }

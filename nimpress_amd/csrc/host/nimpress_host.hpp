@@ -194,8 +194,14 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
                                  ImputeMethodSample imputeMethodSample, double maxMissingRate, double afMismatchPthresh,
                                  int64_t minGtForInternalImput, bool ignoreFilterField, std::vector<Log> &logs,
                                  int device = 0, std::vector<uint64_t> *nloci_out = nullptr, int shard = 0,
-                                 int n_shards = 1, bool partial = false, double *d_out = nullptr);
+                                 int n_shards = 1, bool partial = false, double *d_out = nullptr, bool acceptDs = false);
 // d_out (optional, device memory, [files][n_samples] doubles): results stay on the device, `scores` stays empty.
+// acceptDs (a per-call opt-in; without it a FORMAT/DS record throws, as above): where at least one position of this
+// call's block is scored from FORMAT/DS, the union cohort is a NPS_FMT_DS32 cohort, filled window by window with
+// nps_cohort_upload and scored in two reads for all files (nps_score_cohort_multi on a dosage cohort).  A position whose
+// record is scored from GT (or from .bed / .pgen codes) is decoded on the host to the float32 row of its effect
+// allele's counts and flagged NPS_RIE_COUNTS_EFFECT; warnings come from nps_multi_row_tallies, the same bits the
+// file-by-file path sees.  A block without a FORMAT/DS position takes the 2-bit route unchanged.
 // shard / n_shards / partial: the rows-sharded x all-scores layout over several GPUs.  The
 // union's rows are cut into n_shards contiguous blocks; this call locates, decodes and scores block `shard` only
 // (1 / n_shards of the ingest and of the cohort) for ALL files, and with partial = true returns the state of the

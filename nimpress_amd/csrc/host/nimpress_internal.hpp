@@ -37,6 +37,15 @@ RowClass classifyRow(const ScoreEntry &e, bool restrictToCoveredRgns, const Geno
 void writeRowWarnings(Log &log, const ScoreEntry &e, int kind, const std::string &filter, const std::string &pre_warning,
                       int64_t nsamples, uint64_t nmissing, double neffect, bool over_maxmis, double afMismatchPthresh);
 
+// getRawDosages (nim:367-391) on the host, for the one-pass route over FORMAT/DS files (computePolygenicScoresMulti with
+// acceptDs), whose cohort holds float32 rows: a record scored from GT becomes the row of its effect allele's counts.
+// gts: the typed FORMAT/GT vector as the record holds it (elem_bytes 1 / 2 / 4, n x ploidy values, (allele + 1) << 1 |
+// phased).  Per sample: any missing allele gives NaN; vector-end pads (negative values) are skipped; else the number of
+// alleles equal to eaidx, for any ploidy -- the rule of the device decoders (decode_gt_to_ds_kernel).
+void decodeGtDosage(const void *gts, int elem_bytes, size_t n, int ploidy, int eaidx, float *out);
+// the same for the 2-bit codes of a .bed / .pgen record under its code map (NPS_MAP_*)
+void decodeCodeDosage(const uint8_t *codes, size_t n, int code_map, float *out);
+
 }  // namespace nimpress
 #pragma GCC visibility pop
 

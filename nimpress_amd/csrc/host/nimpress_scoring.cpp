@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -183,6 +184,43 @@ void writeRowWarnings(Log &log, const ScoreEntry &e, int kind, const std::string
 }
 
 // ------------------------------------------------------------------------------------------
+// getRawDosages on the host (nimpress_internal.hpp)
+template <class T>
+static void gtDosageRow(const T *g, size_t n, int ploidy, int eaidx, float *out) {
+    for (size_t i = 0; i < n; ++i) {
+        int cnt = 0;
+        bool miss = false;
+        for (int k = 0; k < ploidy; ++k) {
+            const int32_t a = (int32_t)g[i * (size_t)ploidy + (size_t)k];
+            if (a < 0) continue;  // vector-end pad (a sample of lower ploidy)
+            if (a < 2)
+                miss = true;  // allele value -1
+            else
+                cnt += ((a >> 1) - 1) == eaidx;
+        }
+        out[i] = miss ? std::nanf("") : (float)cnt;
+    }
+}
+void decodeGtDosage(const void *gts, int elem_bytes, size_t n, int ploidy, int eaidx, float *out) {
+    switch (elem_bytes) {
+    case 1: gtDosageRow((const int8_t *)gts, n, ploidy, eaidx, out); break;
+    case 2: gtDosageRow((const int16_t *)gts, n, ploidy, eaidx, out); break;
+    case 4: gtDosageRow((const int32_t *)gts, n, ploidy, eaidx, out); break;
+    default: throw std::runtime_error("decodeGtDosage: FORMAT/GT elements of " + std::to_string(elem_bytes) + " bytes");
+    }
+}
+void decodeCodeDosage(const uint8_t *codes, size_t n, int code_map, float *out) {
+    // .bed: 0 = hom A1, 1 = missing, 2 = het, 3 = hom A2; .pgen: the number of ALT alleles, 3 = missing
+    static const float nanv = std::nanf("");
+    const float table[4][4] = {{0.f, nanv, 1.f, 2.f},   // NPS_MAP_BED_A2
+                               {2.f, nanv, 1.f, 0.f},   // NPS_MAP_BED_A1
+                               {0.f, 1.f, 2.f, nanv},   // NPS_MAP_PGEN_ALT
+                               {2.f, 1.f, 0.f, nanv}};  // NPS_MAP_PGEN_REF
+    if (code_map < 0 || code_map > 3) throw std::runtime_error("decodeCodeDosage: bad code map");
+    for (size_t i = 0; i < n; ++i) out[i] = table[code_map][(codes[i >> 2] >> ((i & 3) * 2)) & 3u];
+}
+
+// ------------------------------------------------------------------------------------------
 // computePolygenicScores  nim:592-649
 void computePolygenicScores(std::vector<double> &scores, const ScoreFile &scoreFile,
                             const VCF &genotypeVcf, bool restrictToCoveredRgns,
@@ -270,7 +308,8 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
                                  ImputeMethodLocus imputeMethodLocus, ImputeMethodMissing imputeMethodMissing,
                                  ImputeMethodSample imputeMethodSample, double maxMissingRate, double afMismatchPthresh,
                                  int64_t minGtForInternalImput, bool ignoreFilterField, std::vector<Log> &logs, int device,
-                                 std::vector<uint64_t> *nloci_out, int shard, int n_shards, bool partial, double *d_out) {
+                                 std::vector<uint64_t> *nloci_out, int shard, int n_shards, bool partial, double *d_out,
+                                 bool acceptDs) {
     if (n_shards < 1 || shard < 0 || shard >= n_shards) throw std::runtime_error("computePolygenicScoresMulti: bad shard");
     warmupJoin();
     const size_t S = scoreFiles.size();
@@ -309,49 +348,92 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
     const size_t A = pos.size() * (size_t)shard / (size_t)n_shards, B = pos.size() * ((size_t)shard + 1) / (size_t)n_shards;
     const size_t U = B - A;
 
-    // ---- locate every position once and decode its record into the resident cohort (nim:526-561)
-    Handle<nps_cohort> gt2 = created<nps_cohort>("nps_cohort_create", [&](nps_cohort **o) {
-        return nps_cohort_create(o, device, (uint64_t)nsamples, (uint64_t)U, NPS_FMT_GT2);
-    });
+    // ---- locate every position once and decode its record into the resident cohort (nim:526-561): a 2-bit cohort,
+    // or -- acceptDs, from the first FORMAT/DS position on: the fill starts again -- a float32 dosage cohort
     std::vector<ScoreEntry> uent(U);
     for (size_t j = 0; j < U; ++j) uent[j] = pos[A + j].e;
-    const size_t window = genotypeVcf.streaming ? streamingWindow(nsamples) : U;
     std::vector<Variant> fetched;
     RecordIndex index;
     if (!genotypeVcf.streaming) index.build(genotypeVcf.records);
-    for (size_t w0 = 0; w0 < U; w0 += window) {
-        const size_t w1 = std::min(U, w0 + window);
-        if (genotypeVcf.streaming) {
-            fetched = genotypeVcf.fetch(uent.data() + w0, w1 - w0);
-            index.build(fetched);
+    Handle<nps_cohort> gt2, dsc;
+    std::vector<unsigned char> from_gt(U, 0);  // dosage cohort: the row holds effect allele counts decoded from GT
+    bool as_ds = false;
+    for (;;) {
+        Handle<nps_cohort> &filled = as_ds ? dsc : gt2;
+        filled = created<nps_cohort>("nps_cohort_create", [&](nps_cohort **o) {
+            return nps_cohort_create(o, device, (uint64_t)nsamples, (uint64_t)U, as_ds ? NPS_FMT_DS32 : NPS_FMT_GT2);
+        });
+        // (dosage rows go up a window at a time: at most 256 MiB of them on the host)
+        const size_t ds_rows = std::max<size_t>((256u << 20) / ((size_t)std::max<int64_t>(nsamples, 1) * 4), 1);
+        const size_t window = genotypeVcf.streaming ? streamingWindow(nsamples) : (as_ds ? std::min(std::max<size_t>(U, 1), ds_rows) : U);
+        std::vector<float> rows, ds_tmp;
+        bool again = false;
+        for (size_t w0 = 0; w0 < U && !again; w0 += window) {
+            const size_t w1 = std::min(U, w0 + window);
+            if (genotypeVcf.streaming) {
+                fetched = genotypeVcf.fetch(uent.data() + w0, w1 - w0);
+                index.build(fetched);
+            }
+            if (as_ds) rows.assign((w1 - w0) * (size_t)nsamples, 0.0f);
+            for (size_t j = w0; j < w1; ++j) {  // (cohort row j = position A + j)
+                Position &q = pos[A + j];
+                RowClass c = classifyRow(q.e, restrictToCoveredRgns, coveredIvals, index, ignoreFilterField);
+                const Variant *v = c.v;
+                q.how = c.kind;
+                q.filter = std::move(c.filter);
+                q.pre_warning = std::move(c.pre_warning);
+                if (c.kind) continue;
+                Tick tick(timings().push);
+                if (as_ds) {
+                    float *row = rows.data() + (j - w0) * (size_t)nsamples;
+                    if (v->has_ds) {
+                        memcpy(row, v->dsRow(c.eaidx, (size_t)nsamples, ds_tmp), sizeof(float) * (size_t)nsamples);
+                    } else {
+                        from_gt[j] = 1;
+                        if (v->is_bed || v->is_pgen)
+                            decodeCodeDosage(v->gt_raw.data(), (size_t)nsamples, c.code_map, row);
+                        else
+                            decodeGtDosage(v->gtData(), v->gt_raw.empty() ? 4 : v->gt_bytes, (size_t)nsamples, v->ploidy, c.eaidx, row);
+                    }
+                    continue;
+                }
+                if (v->has_ds) {
+                    if (!acceptDs) throw std::runtime_error("FORMAT/DS records are not covered by the one-pass multi-score path");
+                    again = true;  // the block holds dosages: fill a float32 cohort from its first row on
+                    break;
+                }
+                if (v->is_bed || v->is_pgen)
+                    npsCheck(nps_cohort_push_bed(gt2.get(), j, v->gt_raw.data(), c.code_map), "nps_cohort_push_bed");
+                else
+                    npsCheck(nps_cohort_push_gt_raw(gt2.get(), j, v->gtData(), v->gt_raw.empty() ? 4 : v->gt_bytes, v->ploidy,
+                                                    c.eaidx),
+                             "nps_cohort_push_gt_raw");
+            }
+            if (as_ds && !again && nsamples > 0) {
+                Tick tick(timings().push);
+                npsCheck(nps_cohort_upload(dsc.get(), w0, w1 - w0, rows.data(), sizeof(float) * (size_t)nsamples), "nps_cohort_upload");
+            }
         }
-        for (size_t j = w0; j < w1; ++j) {  // (cohort row j = position A + j)
-            Position &q = pos[A + j];
-            RowClass c = classifyRow(q.e, restrictToCoveredRgns, coveredIvals, index, ignoreFilterField);
-            const Variant *v = c.v;
-            q.how = c.kind;
-            q.filter = std::move(c.filter);
-            q.pre_warning = std::move(c.pre_warning);
-            if (c.kind) continue;
-            if (v->has_ds) throw std::runtime_error("FORMAT/DS records are not covered by the one-pass multi-score path");
-            Tick tick(timings().push);
-            if (v->is_bed || v->is_pgen)
-                npsCheck(nps_cohort_push_bed(gt2.get(), j, v->gt_raw.data(), c.code_map), "nps_cohort_push_bed");
-            else
-                npsCheck(nps_cohort_push_gt_raw(gt2.get(), j, v->gtData(), v->gt_raw.empty() ? 4 : v->gt_bytes, v->ploidy,
-                                                c.eaidx),
-                         "nps_cohort_push_gt_raw");
-        }
+        if (!again) break;
+        as_ds = true;
+        gt2.reset();
     }
     fetched.clear();
     double t_kernels0 = nowSeconds();
-    const Handle<nps_cohort> gt2m = created<nps_cohort>("nps_cohort_create", [&](nps_cohort **o) {
-        return nps_cohort_create(o, device, (uint64_t)nsamples, (uint64_t)U, NPS_FMT_GT2M);
-    });
-    npsCheck(nps_cohort_convert(gt2m.get(), gt2.get()), "nps_cohort_convert");
-    gt2.reset();
-    std::vector<uint64_t> nmiss(U, 0), neff(U, 0);
-    if (U) npsCheck(nps_cohort_row_tallies(gt2m.get(), 0, U, nmiss.data(), neff.data()), "nps_cohort_row_tallies");
+    Handle<nps_cohort> gt2m;
+    std::vector<uint64_t> nmiss(U, 0);
+    std::vector<double> neff(U, 0.0);  // effect alleles of the genotyped samples: a count, or a dosage sum
+    if (!as_ds) {
+        gt2m = created<nps_cohort>("nps_cohort_create", [&](nps_cohort **o) {
+            return nps_cohort_create(o, device, (uint64_t)nsamples, (uint64_t)U, NPS_FMT_GT2M);
+        });
+        npsCheck(nps_cohort_convert(gt2m.get(), gt2.get()), "nps_cohort_convert");
+        gt2.reset();
+        std::vector<uint64_t> counts(U, 0);
+        if (U) npsCheck(nps_cohort_row_tallies(gt2m.get(), 0, U, nmiss.data(), counts.data()), "nps_cohort_row_tallies");
+        for (size_t j = 0; j < U; ++j) neff[j] = (double)counts[j];
+    }
+    const nps_cohort *const cohort = as_ds ? dsc.get() : gt2m.get();
 
     // ---- the definitions, NPS_MULTI_MAX_SCORES files at a time
     for (size_t s0 = 0; s0 < S; s0 += NPS_MULTI_MAX_SCORES) {
@@ -375,7 +457,7 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
                 d.beta = sf.entries[r].beta;
                 d.eaf = sf.entries[r].eaf;
                 d.kind = pos[A + j].how ? pos[A + j].how : NPS_ROW_PRESENT;
-                d.ref_is_effect = sf.entries[r].refseq == sf.entries[r].easeq ? 1 : 0;
+                d.ref_is_effect = (sf.entries[r].refseq == sf.entries[r].easeq ? 1 : 0) | (from_gt[j] ? NPS_RIE_COUNTS_EFFECT : 0);
             }
         }
         // (released at the end of each round in reverse order: the scorer before its definitions)
@@ -384,7 +466,15 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
         });
         const Handle<nps_multi> msc = created<nps_multi>(
             "nps_multi_create", [&](nps_multi **o) { return nps_multi_create(o, device, (uint64_t)nsamples, &p, (int)ns); });
-        if (U) npsCheck(nps_score_cohort_multi(msc.get(), gt2m.get(), 0, mdef.get()), "nps_score_cohort_multi");
+        if (U) npsCheck(nps_score_cohort_multi(msc.get(), cohort, 0, mdef.get()), "nps_score_cohort_multi");
+        if (U && as_ds && s0 == 0) {
+            // the rows' tallies for the warnings: the row's, whichever batch of files lists it (every pass counts all rows);
+            // the flipped sum where the row's dosage is 2 - DS
+            std::vector<double> sum(U), flipped(U);
+            npsCheck(nps_multi_row_tallies(msc.get(), 0, U, nmiss.data(), sum.data(), flipped.data()), "nps_multi_row_tallies");
+            for (size_t j = 0; j < U; ++j)
+                neff[j] = !from_gt[j] && pos[A + j].e.refseq == pos[A + j].e.easeq ? flipped[j] : sum[j];
+        }
         std::vector<double> offs(ns), flat(ns * (size_t)std::max<int64_t>(nsamples, 1));
         std::vector<uint64_t> nl(ns, 0);
         for (size_t s = 0; s < ns; ++s) offs[s] = scoreFiles[s0 + s]->offset;
@@ -415,8 +505,8 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
             const Position &q = pos[rows_of[s][r]];
             const size_t j = rows_of[s][r] - A;
             const bool over_maxmis = (double)nmiss[j] / (double)nsamples > maxMissingRate;  // nim:565
-            writeRowWarnings(logs[s], sf.entries[r], q.how, q.filter, q.pre_warning, nsamples, nmiss[j], (double)neff[j],
-                             over_maxmis, afMismatchPthresh);
+            writeRowWarnings(logs[s], sf.entries[r], q.how, q.filter, q.pre_warning, nsamples, nmiss[j], neff[j], over_maxmis,
+                             afMismatchPthresh);
         }
     }
 }

@@ -2021,7 +2021,7 @@ extern "C" int nps_score_cohort(nps_ctx *c, const nps_cohort *co, uint64_t cohor
 }
 
 // ------------------------------------------------------------------------------------------
-// several score definitions in one pass over a NPS_FMT_GT2M cohort (nps_multi.hip)
+// several score definitions in one pass over a NPS_FMT_GT2M cohort (nps_multi.hip), in two over a dosage cohort (nps_multi_ds.hip)
 extern "C" int nps_cohort_convert(nps_cohort *dst, const nps_cohort *src) {
     if (!dst || !src) return fail(NPS_E_INVAL, "cohort is NULL");
     if ((dst->format != NPS_FMT_GT2M && dst->format != NPS_FMT_GT2X) || src->format != NPS_FMT_GT2)
@@ -2240,6 +2240,13 @@ struct nps_multi {
     bool timed = false;
     int coarse_missing = 0;          // nps_multi_set_missing_weight_bits: leading base-256 digits kept (4 = 32 bits, 5 = 40; 0 = all)
     bool broken = false;             // a HIP call failed between the first and the last launch of a pass
+    // dosage cohorts (nps_multi_ds.hip), grown on demand: the row tallies and the (row, score) records of the last such
+    // pass, the partial planes of its row chunks
+    DevBuf<MultiDsTally> d_ds_tally;
+    DevBuf<DsRowP> d_ds_rowp;
+    DevBuf<double> d_ds_planes;
+    uint64_t ds_rows = 0;            // rows of the most recent call if it was on a dosage cohort (nps_multi_row_tallies)
+    bool ds_last = false;
 
     ~nps_multi() {  // queued work may still use what the members release
         (void)hipSetDevice(device);
@@ -2317,7 +2324,55 @@ extern "C" int nps_multi_reset(nps_multi *m, const nps_params *params) {
     HIP_TRY(hipMemsetAsync(m->d_state.get(), 0, multi_state_bytes() * NPS_MULTI_MAX_SCORES, m->stream.get()));
     m->broken = false;
     m->have_sums = false;
+    m->ds_last = false;
+    m->ds_rows = 0;
     m->ms[0] = m->ms[1] = m->ms[2] = 0.0;
+    return NPS_OK;
+}
+
+// A dosage cohort (nps_multi_ds.hip): one tally read of the rows, one accumulation read for all S scores.  The caller has
+// checked the arguments and made the device current.  nps_multi_set_missing_weight_bits has no meaning here: float64.
+static int multi_score_ds(nps_multi *m, const nps_cohort *co, uint64_t cohort_row0, const nps_multidef *def) {
+    const uint64_t rows = def->n_desc;
+    const int elem = co->format == NPS_FMT_DS16 ? 2 : 4;
+    const uint64_t stride_e = co->stride_bytes / elem;
+    const void *ds = (const char *)co->d_data.get() + cohort_row0 * co->stride_bytes;
+    const MultiDsPlan pl = multi_ds_plan(m->n, rows, m->cus);
+    if (rows > 0x7fffffffull) return fail(NPS_E_UNSUPPORTED, "too many rows for one call");
+    HIP_TRY(m->d_ds_tally.ensure(rows, m->stream.get()));
+    HIP_TRY(m->d_ds_rowp.ensure(rows * m->S, m->stream.get()));
+    HIP_TRY(m->d_ds_planes.ensure(pl.plane_elems(m->S), m->stream.get()));
+    if (m->timed && hipEventQuery(m->ev[3].get()) == hipSuccess) multi_drain_timing(m);
+    m->timed = false;
+    // Everything that can be refused has been checked and allocated (see nps_score_cohort_multi).
+    auto run = [&]() -> hipError_t {
+        hipError_t e = hipEventRecord(m->ev[0].get(), m->stream.get());
+        if (e != hipSuccess) return e;
+        e = launch_multi_ds_tally(m->stream.get(), ds, elem, stride_e, m->n, rows, m->d_ds_tally.get());
+        if (e != hipSuccess) return e;
+        e = launch_multi_ds_params(m->stream.get(), m->d_ds_tally.get(), def->d_desc.get(), rows, m->S, m->n, dev_params(m->params),
+                                   m->d_ds_rowp.get(), m->d_state.get());
+        if (e != hipSuccess) return e;
+        e = hipEventRecord(m->ev[1].get(), m->stream.get());
+        if (e != hipSuccess) return e;
+        e = launch_multi_ds_accumulate(m->stream.get(), pl, ds, elem, stride_e, m->n, m->d_ds_rowp.get(), rows, m->S,
+                                       m->d_ds_planes.get());
+        if (e != hipSuccess) return e;
+        e = hipEventRecord(m->ev[2].get(), m->stream.get());
+        if (e != hipSuccess) return e;
+        e = launch_multi_ds_fold(m->stream.get(), pl, m->d_ds_planes.get(), m->n, m->S, m->d_part.get(), m->have_sums ? 0 : 1);
+        if (e != hipSuccess) return e;
+        return hipEventRecord(m->ev[3].get(), m->stream.get());
+    };
+    const hipError_t e = run();
+    if (e != hipSuccess) {
+        m->broken = true;
+        return fail(NPS_E_HIP, "nps_score_cohort_multi: %s (context needs nps_multi_reset)", hipGetErrorString(e));
+    }
+    m->have_sums = true;
+    m->timed = true;
+    m->ds_last = true;
+    m->ds_rows = rows;
     return NPS_OK;
 }
 
@@ -2325,7 +2380,9 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
                                       const nps_multidef *def) {
     if (!m || !co || !def) return fail(NPS_E_INVAL, "ctx, cohort or definitions is NULL");
     if (m->broken) return fail(NPS_E_STATE, "an earlier pass failed on the device: nps_multi_reset first");
-    if (co->format != NPS_FMT_GT2M) return fail(NPS_E_INVAL, "nps_score_cohort_multi needs a NPS_FMT_GT2M cohort");
+    const bool is_ds = co->format == NPS_FMT_DS32 || co->format == NPS_FMT_DS16;
+    if (co->format != NPS_FMT_GT2M && !is_ds)
+        return fail(NPS_E_INVAL, "nps_score_cohort_multi needs a NPS_FMT_GT2M, NPS_FMT_DS32 or NPS_FMT_DS16 cohort");
     if (co->device != m->device || def->device != m->device)
         return fail(NPS_E_INVAL, "cohort / definitions / context on different devices");
     if (co->n_samples != m->n)
@@ -2337,6 +2394,7 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
     if (rc) return rc;
     if (def->n_desc == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(m->device));
+    if (is_ds) return multi_score_ds(m, co, cohort_row0, def);
     const MultiPlan pl = multi_plan(m->n, def->n_desc, m->S, def->ND, m->coarse_missing, m->cus);
     HIP_TRY(m->d_table.ensure(pl.table_bytes() + pl.flag_bytes(), m->stream.get()));
     HIP_TRY(m->d_partial.ensure(pl.partial_elems(), m->stream.get()));
@@ -2375,6 +2433,40 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
     }
     m->have_sums = true;
     m->timed = true;
+    m->ds_last = false;
+    return NPS_OK;
+}
+
+extern "C" int nps_multi_row_tallies(nps_multi *m, uint64_t first, uint64_t n, uint64_t *nmissing_out, double *sum_out,
+                                     double *sum_flipped_out) {
+    if (!m) return fail(NPS_E_INVAL, "ctx is NULL");
+    if (m->broken) return fail(NPS_E_STATE, "an earlier pass failed on the device: nps_multi_reset first");
+    if (!m->ds_last)
+        return fail(NPS_E_STATE, "nps_multi_row_tallies: the most recent nps_score_cohort_multi call of this context was not "
+                                 "on a NPS_FMT_DS32 / NPS_FMT_DS16 cohort (or the context was reset since)");
+    if (first > m->ds_rows || n > m->ds_rows - first)
+        return fail(NPS_E_INVAL, "rows %llu + %llu outside the %llu rows of the last pass", (unsigned long long)first,
+                    (unsigned long long)n, (unsigned long long)m->ds_rows);
+    if (n == 0) return NPS_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    std::vector<MultiDsTally> t(n);
+    HIP_TRY(hipMemcpyAsync(t.data(), m->d_ds_tally.get() + first, sizeof(MultiDsTally) * n, hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    for (uint64_t j = 0; j < n; ++j) {
+        if (nmissing_out) nmissing_out[j] = t[j].nmiss;
+        if (sum_out) sum_out[j] = t[j].sum;
+        if (sum_flipped_out) sum_flipped_out[j] = t[j].sum_flipped;
+    }
+    return NPS_OK;
+}
+
+extern "C" int nps_multi_geometry(const nps_multi *m, int format, uint64_t n_rows, uint32_t *row_chunks, uint32_t *rows_per_chunk) {
+    if (!m) return fail(NPS_E_INVAL, "ctx is NULL");
+    if (format == NPS_FMT_GT2M) return fail(NPS_E_UNSUPPORTED, "nps_multi_geometry reports the plan of dosage cohorts");
+    if (format != NPS_FMT_DS32 && format != NPS_FMT_DS16) return fail(NPS_E_INVAL, "format %d is not a dosage format", format);
+    const MultiDsPlan pl = multi_ds_plan(m->n, n_rows, m->cus);  // (one plan for both element types)
+    if (row_chunks) *row_chunks = pl.n_chunks;
+    if (rows_per_chunk) *rows_per_chunk = (uint32_t)std::min<uint64_t>(pl.rows_per_chunk, 0xffffffffull);
     return NPS_OK;
 }
 

@@ -248,6 +248,14 @@ struct MultiPlan {
     uint64_t flag_bytes() const { return (uint64_t)n_sb * 4; }  // one word per superblock, behind the tables
     uint64_t partial_elems() const { return (uint64_t)n_chunks * n_groups * 32 * T * 16; }
 };
+struct MultiState {          // per score, on the device
+    unsigned long long nloci;  // rows for which getImputedDosages returned true
+    long long const_lo, const_hi;  // whole-locus constants of this call in fixed point: (hi << 32) + lo
+    unsigned long long const_nan;  // a whole-locus constant was NaN (imp-locus fail / NaN eaf)
+    double const_sum;          // float64 sum over the calls so far
+    unsigned long long m_low;  // (score 0 only) m_flag: a NaN imputation value occurred in this call (flag tiles needed)
+    double pad[2];
+};
 MultiPlan multi_plan(uint64_t n_samples, uint64_t n_rows, int S, int ND, int coarse_missing /* leading base-256 digits of the is-missing weights kept: 4, 5; 0 = all */, int cus);
 size_t multi_state_bytes();
 hipError_t launch_multi_params(hipStream_t st, const unsigned long long *d_tally, const nps_row_desc *d_desc,
@@ -260,6 +268,33 @@ hipError_t launch_multi_fold(hipStream_t st, const MultiPlan &pl, const int32_t 
                              const int *d_F, double *d_part, int overwrite, void *d_state);
 hipError_t launch_multi_finish(hipStream_t st, const double *d_part, uint64_t n_samples, int S, const void *d_state,
                                const double *d_offsets, int have_sums, double *d_scores, int normalise = 1);
+
+// ---- several scores in two reads of a dosage cohort, NPS_FMT_DS32 / NPS_FMT_DS16 (nps_multi_ds.hip) ----------
+struct MultiDsTally {  // per cohort row, whatever the scores make of it
+    unsigned long long nmiss;
+    double sum, sum_flipped;  // sum of DS and of 2 - DS over the non-missing samples
+};
+// The accumulation's row chunks (grid.y).  A function of the cohort's shape and the chip alone, never of the number of
+// scores: a definition's column has the same bits whatever other definitions share the pass.
+struct MultiDsPlan {
+    uint32_t n_chunks = 0;
+    uint64_t rows_per_chunk = 0;
+    uint64_t plane_stride = 0;  // doubles per (chunk, score) plane: the samples rounded up to whole lanes of four
+    uint64_t plane_elems(int S) const { return (uint64_t)n_chunks * S * plane_stride; }
+};
+MultiDsPlan multi_ds_plan(uint64_t n_samples, uint64_t n_rows, int cus);
+// elem_bytes 4: float32 rows; 2: NPS_FMT_DS16 rows.  stride_e: elements per row
+hipError_t launch_multi_ds_tally(hipStream_t st, const void *d_ds, int elem_bytes, uint64_t stride_e, uint64_t n,
+                                 uint64_t n_rows, MultiDsTally *d_tally);
+// d_desc: [S][n_desc]; d_rowp: [n_desc][S] (the S records of a row side by side); adds the used rows to MultiState::nloci
+hipError_t launch_multi_ds_params(hipStream_t st, const MultiDsTally *d_tally, const nps_row_desc *d_desc, uint64_t n_desc,
+                                  int S, uint64_t n_samples, DevParams p, DsRowP *d_rowp, void *d_state);
+// d_planes: [pl.n_chunks][S][pl.plane_stride], every element of the chunks' planes is written
+hipError_t launch_multi_ds_accumulate(hipStream_t st, const MultiDsPlan &pl, const void *d_ds, int elem_bytes, uint64_t stride_e,
+                                      uint64_t n, const DsRowP *d_rowp, uint64_t n_rows, int S, double *d_planes);
+// part[s][i] (+)= the planes of the chunks, in chunk order (overwrite != 0: part holds nothing yet)
+hipError_t launch_multi_ds_fold(hipStream_t st, const MultiDsPlan &pl, const double *d_planes, uint64_t n, int S, double *d_part,
+                                int overwrite);
 
 // ---- single-read kernel on the matrix cores for the strip layout NPS_FMT_GT2X (nps_mx.hip) -----------------
 // layout, geometry (MxGeom), plan (MxPlan) and route (mx_route): nps_mx_route.h, free of HIP

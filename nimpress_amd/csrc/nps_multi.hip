@@ -302,14 +302,7 @@ static __device__ __forceinline__ void weight_digits(long long V, int ND, int ke
     d[7] = 0;
 }
 
-struct MultiState {          // per score, on the device
-    unsigned long long nloci;  // rows for which getImputedDosages returned true
-    long long const_lo, const_hi;  // whole-locus constants of this call in fixed point: (hi << 32) + lo
-    unsigned long long const_nan;  // a whole-locus constant was NaN (imp-locus fail / NaN eaf)
-    double const_sum;          // float64 sum over the calls so far
-    unsigned long long m_low;  // (score 0 only) m_flag: a NaN imputation value occurred in this call (flag tiles needed)
-    double pad[2];
-};
+// (MultiState, per score on the device: nps_kernels.h)
 
 // One thread per (superblock, row quarter g, word i, score slot s): the 16 rows 128 sb + 32 g + 16 i + 4 b + f
 // (b = byte, f = field) -- whole bytes, because the prefix basis couples the four fields of a byte.  It writes

@@ -42,6 +42,14 @@ def load():
         L.nh_compute_multi_dev.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                            C.c_double, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_char_p, C.c_long]
+        L.nh_compute_multi_ex.restype = C.c_long
+        L.nh_compute_multi_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                          C.c_double, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint,
+                                          C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_long]
+        L.nh_decode_gt_dosage.restype = C.c_long
+        L.nh_decode_gt_dosage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+        L.nh_decode_code_dosage.restype = C.c_long
+        L.nh_decode_code_dosage.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p]
         L.nh_last_log_size.restype = C.c_long
         L.nh_last_log.restype = C.c_long
         L.nh_last_log.argtypes = [C.c_char_p, C.c_long]
@@ -75,6 +83,34 @@ def _full_log(L, buf) -> str:
     big = C.create_string_buffer(size + 1)
     L.nh_last_log(big, len(big))
     return big.value.decode("utf-8", "replace")
+
+
+MULTI_ACCEPT_DS = 1   # flags of nh_compute_multi_ex: FORMAT/DS records are scored too (dosage rows, two reads)
+
+
+def decode_gt_dosage(gt: np.ndarray, ploidy: int, eaidx: int) -> np.ndarray:
+    """the host's decode of a typed FORMAT/GT vector (int8 / int16 / int32, n x ploidy values) into the float32 row of
+    effect allele counts that the one-pass dosage route uploads (NaN = a missing allele)"""
+    gt = np.ascontiguousarray(gt)
+    if gt.dtype not in (np.int8, np.int16, np.int32) or gt.size % ploidy:
+        raise ValueError("gt must be int8 / int16 / int32 with n * ploidy values")
+    out = np.empty(max(gt.size // ploidy, 1), dtype=np.float32)
+    n = load().nh_decode_gt_dosage(gt.ctypes.data, gt.dtype.itemsize, gt.size // ploidy, int(ploidy), int(eaidx), out.ctypes.data)
+    if n < 0:
+        raise capi.NpsError(-1, "nh_decode_gt_dosage: bad arguments")
+    return out[:n]
+
+
+def decode_code_dosage(codes: np.ndarray, n: int, code_map: int) -> np.ndarray:
+    """the same for the ceil(n / 4) bytes of a .bed / .pgen record under its code map (NPS_MAP_*: 0 / 1 .bed A2 / A1,
+    2 / 3 .pgen ALT / REF)"""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if codes.size < (n + 3) // 4:
+        raise ValueError("codes too short")
+    out = np.empty(max(n, 1), dtype=np.float32)
+    if load().nh_decode_code_dosage(codes.ctypes.data, int(n), int(code_map), out.ctypes.data) < 0:
+        raise capi.NpsError(-1, "nh_decode_code_dosage: bad arguments")
+    return out[:n]
 
 
 TIMING_KEYS = ("hip_init_s", "hip_init_wait_s", "open_s", "inflate_parse_s", "push_s", "kernel_s", "warnings_s")
@@ -115,12 +151,13 @@ def compute_polygenic_scores(score_path: str, vcf_path: str, cov: Optional[str] 
 def compute_polygenic_scores_multi(score_paths, vcf_path: str, cov: Optional[str] = None, imp_locus: str = "ps",
                                    imp_missing: str = "homref", imp_sample: str = "int_ps", maxmis: float = 0.05,
                                    mincs: int = 100, afmisp: float = 0.001, ignorefilt: bool = False, device: int = 0,
-                                   max_samples: int = 1 << 22, d_out: Optional[int] = None):
+                                   max_samples: int = 1 << 22, d_out: Optional[int] = None, accept_ds: bool = False):
     """Several score files on one genotype file in ONE pass over the genotypes (computePolygenicScoresMulti: the union
     of the files' loci decoded once into a resident cohort, all definitions applied together on the matrix cores).
     Returns (scores [files, samples], nloci [files], log lines per file).  d_out: a device pointer to
     [files, samples] doubles (samples = the cohort's) -- the scores are left there (nps_multi_finish_device) and None is
-    returned for them."""
+    returned for them.  accept_ds: FORMAT/DS records are scored too -- a float32 dosage cohort, two reads for all files --
+    instead of being an error."""
     L = load()
     S = len(score_paths)
     nloci = np.zeros(S, dtype=np.uint64)
@@ -128,7 +165,11 @@ def compute_polygenic_scores_multi(score_paths, vcf_path: str, cov: Optional[str
     args = ("\n".join(score_paths).encode(), vcf_path.encode(), cov.encode() if cov else None,
             capi.LOCUS[imp_locus], capi.MISSING[imp_missing], capi.SAMPLE[imp_sample], float(maxmis),
             float(afmisp), int(mincs), int(ignorefilt), device)
-    if d_out is not None:
+    if accept_ds:
+        scores = None if d_out is not None else np.empty((S, max_samples), dtype=np.float64)
+        n = L.nh_compute_multi_ex(*args, 0, 1, 0, MULTI_ACCEPT_DS, None if scores is None else scores.ctypes.data, max_samples,
+                                  None if d_out is None else C.c_void_p(int(d_out)), nloci.ctypes.data, None, log, len(log))
+    elif d_out is not None:
         scores = None
         n = L.nh_compute_multi_dev(*args, 0, 1, 0, C.c_void_p(int(d_out)), nloci.ctypes.data, None, log, len(log))
     else:
@@ -154,7 +195,8 @@ def compute_polygenic_scores_multi_partial(score_paths, vcf_path: str, shard: in
                                            imp_locus: str = "ps", imp_missing: str = "homref",
                                            imp_sample: str = "int_ps", maxmis: float = 0.05, mincs: int = 100,
                                            afmisp: float = 0.001, ignorefilt: bool = False, device: int = 0,
-                                           max_samples: int = 1 << 22, d_out: Optional[int] = None):
+                                           max_samples: int = 1 << 22, d_out: Optional[int] = None,
+                                           accept_ds: bool = False):
     """Rows sharded over several GPUs x ALL score files on each: block `shard` of `n_shards` of
     the union of the files' loci is located, decoded and scored on this GPU -- 1 / n_shards of the ingest and of the
     cohort.  Returns (sums [files, samples] BEFORE the normalisation, nloci [files] of the block, offsets [files],
@@ -168,7 +210,12 @@ def compute_polygenic_scores_multi_partial(score_paths, vcf_path: str, shard: in
     args = ("\n".join(score_paths).encode(), vcf_path.encode(), cov.encode() if cov else None,
             capi.LOCUS[imp_locus], capi.MISSING[imp_missing], capi.SAMPLE[imp_sample],
             float(maxmis), float(afmisp), int(mincs), int(ignorefilt), device, int(shard), int(n_shards))
-    if d_out is not None:   # the block's sums stay on the device for the all-reduce (nps_multi_partial_device)
+    if accept_ds:           # (FORMAT/DS records are scored too: compute_polygenic_scores_multi)
+        sums = None if d_out is not None else np.zeros((S, max_samples), dtype=np.float64)
+        n = L.nh_compute_multi_ex(*args, 1, MULTI_ACCEPT_DS, None if sums is None else sums.ctypes.data, max_samples,
+                                  None if d_out is None else C.c_void_p(int(d_out)), nloci.ctypes.data, offsets.ctypes.data,
+                                  log, len(log))
+    elif d_out is not None:   # the block's sums stay on the device for the all-reduce (nps_multi_partial_device)
         sums = None
         n = L.nh_compute_multi_dev(*args, 1, C.c_void_p(int(d_out)), nloci.ctypes.data, offsets.ctypes.data, log, len(log))
     else:
