@@ -184,6 +184,30 @@ int nps_push_bed(nps_ctx *ctx, const uint8_t *bed_row, int effect_is_a1, int ref
  * n_samples float32 ALT dosages, NaN = missing; ref_is_effect -> dosage = 2 - DS. */
 int nps_push_ds(nps_ctx *ctx, const float *ds, int ref_is_effect, double beta, double eaf);
 
+/* PRESENT row with FORMAT/PL, the phred-scaled genotype likelihoods of a DIPLOID sample (build-defined extension: the
+ * reference decodes GT only and lists this under "Future"; there is nothing to pin parity against).  The row scored is
+ * the expected count of the effect allele under a FLAT genotype prior (no Hardy-Weinberg prior from eaf), decoded on the
+ * device.
+ *   pl: n_samples x G values of elem_bytes = 1, 2 or 4 bytes (int8 / int16 / int32, the typed vector as a BCF2 record
+ *     holds it), G = A (A + 1) / 2 for a record of A = n_alleles alleles (REF + ALTs), 2 <= A <= 8 (NPS_E_UNSUPPORTED
+ *     otherwise).  Genotype (j, k), j <= k, has index k (k + 1) / 2 + j (the order of the VCF specification).  Values
+ *     are sign-extended from their width: the BCF missing and end-of-vector values are negative in every width.
+ *   missing (NaN in the row, handed to the imputation chain): a sample with ANY negative value, or with
+ *     max PL == min PL -- an uninformative vector such as the 0,0,0 of a sample without reads is not dosage 1.
+ *   likelihoods: w_g = T[min(PL_g, 255)], T[k] = pow(10.0, -(double)k / 10.0): a float64 table of 256 entries built
+ *     once on the host (nps_pl_likelihoods hands out the same values).  PL above 255 counts as 255 (10^-25.5).
+ *   dosage of effect allele e = eaidx (0 = REF, k = ALT[k-1]; 0 <= e < A, NPS_E_INVAL otherwise):
+ *     cnt_e(g) = (j == e) + (k == e);  num = sum_g cnt_e(g) w_g,  den = sum_g w_g, both in float64, added in ascending
+ *     g, one rounding per add (the products are exact);  row value = (float)(num / den), in [0, 2].
+ * The row counts the effect allele itself -- there is no 2 - DS -- and ref_is_effect only selects the homref imputation
+ * value, exactly as for the rows of a polyploid nps_push_gt; statistics are those of a FORMAT/DS row (neffect a float64
+ * sum).  elem_bytes outside {1, 2, 4}, a bad eaidx or pl == NULL with n_samples > 0: NPS_E_INVAL.  A refused call
+ * changes nothing. */
+int nps_push_pl(nps_ctx *ctx, const void *pl, int elem_bytes, int n_alleles, int eaidx, int ref_is_effect,
+                double beta, double eaf);
+/* out256[k] = T[k] of nps_push_pl, k = 0 .. 255.  Needs no device. */
+int nps_pl_likelihoods(double *out256);
+
 /* PRESENT row already as 2-bit codes: ceil(n_samples/16) little-endian uint32, sample i
  * in bits 2*(i%16).. of word i/16 (the library re-orders the bits of a word for its own layout); codes NPS_CODE_*: 0 = dosage 0, 1 = dosage 1, 3 = dosage 2,
  * 2 = missing (so that popcount(word) = effect alleles + missing samples); padding bits zero.
@@ -317,6 +341,16 @@ int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrows, const ui
  * caller may reuse its buffer on return; calls that read the cohort wait for the pushed rows. */
 int nps_cohort_push_gt_raw(nps_cohort *c, uint64_t row, const void *gt, int elem_bytes, int ploidy, int eaidx);
 int nps_cohort_push_bed(nps_cohort *c, uint64_t row, const uint8_t *bed_row, int effect_is_a1);
+/* One row of a NPS_FMT_DS32 cohort from the FORMAT/PL vector of a record (see nps_push_pl: same arguments, same
+ * arithmetic, same kernel), with the cohort as the destination; any other format: NPS_E_UNSUPPORTED.  Ordering as for
+ * nps_cohort_push_gt_raw: the caller may reuse its buffer on return, calls that read the cohort wait for the pushed
+ * rows.  The values written are in [0, 2] or NaN, so the cohort's out-of-range state (NPS_FMT_DS32 above) is untouched:
+ * a push never sets it, and it does not clear it either -- a row that nps_cohort_upload found out of range stays marked
+ * after a PL row is pushed over it (the cohort keeps to the two-pass kernels under NPS_MODE_AUTO: slower, never wrong)
+ * until nps_cohort_upload writes that row again.
+ * Such a row ALREADY counts the effect allele: the descriptors that score it carry
+ * (ea == ref ? 1 : 0) | NPS_RIE_COUNTS_EFFECT in ref_is_effect (nps_score_cohort[_def], nps_score_cohort_multi). */
+int nps_cohort_push_pl(nps_cohort *c, uint64_t row, const void *pl, int elem_bytes, int n_alleles, int eaidx);
 /* Fill rows on the device with the counter-based synthetic generator (DESIGN.md "Synthetic
  * cohorts"): per-row uint32 thresholds, code(seed,row,sample) reproducible on the CPU. */
 /* One-time layout change of a resident 2-bit cohort (no-op for the other formats): inside every group of

@@ -66,6 +66,7 @@ SYMBOLS = [
     "nps_cohort_push_gt_raw", "nps_cohort_push_bed", "nps_multi_partial_device", "nps_multi_partial",
     "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes", "nps_cohort_rows_tallied",
     "nps_live_resources", "nps_multi_row_tallies", "nps_multi_geometry",
+    "nps_push_pl", "nps_cohort_push_pl", "nps_pl_likelihoods",
 ]
 
 
@@ -211,6 +212,9 @@ def load(with_torch: bool = True):
     L.nps_cohort_rows_tallied.argtypes = [vp, u64, u64]
     L.nps_cohort_push_gt_raw.argtypes = [vp, u64, vp, i32, i32, i32]
     L.nps_cohort_push_bed.argtypes = [vp, u64, vp, i32]
+    L.nps_push_pl.argtypes = [vp, vp, i32, i32, i32, i32, dbl, dbl]
+    L.nps_cohort_push_pl.argtypes = [vp, u64, vp, i32, i32, i32]
+    L.nps_pl_likelihoods.argtypes = [vp]
     L.nps_live_resources.argtypes = []
     L.nps_live_resources.restype = C.c_int64
     _lib = L
@@ -231,6 +235,22 @@ def make_params(imp_locus="ps", imp_missing="homref", imp_sample="int_ps", maxmi
 
 def device_count() -> int:
     return load().nps_device_count()
+
+
+def pl_likelihoods() -> np.ndarray:
+    """the 256 float64 likelihoods T[k] = 10^(-k/10) of the FORMAT/PL decode (nps_pl_likelihoods; needs no device)"""
+    out = np.zeros(256, dtype=np.float64)
+    _check(load().nps_pl_likelihoods(out.ctypes.data))
+    return out
+
+
+def _pl_vector(pl: np.ndarray, n: int, n_alleles: int) -> np.ndarray:
+    pl = np.ascontiguousarray(pl)
+    if pl.dtype not in (np.int8, np.int16, np.int32):
+        raise ValueError("pl dtype must be int8, int16 or int32")
+    if 2 <= n_alleles <= 8 and pl.size != n * (n_alleles * (n_alleles + 1) // 2):
+        raise ValueError("pl has %d values, expected %d" % (pl.size, n * (n_alleles * (n_alleles + 1) // 2)))
+    return pl
 
 
 def live_resources() -> int:
@@ -304,6 +324,13 @@ class Cohort:
         bed_row = np.ascontiguousarray(bed_row, dtype=np.uint8)
         assert bed_row.size == (self.n_samples + 3) // 4
         _check(load().nps_cohort_push_bed(self._h, int(row), bed_row.ctypes.data, int(effect_is_a1)))
+
+    def push_pl(self, row: int, pl: np.ndarray, n_alleles: int, eaidx: int):
+        """one row of a FMT_DS32 cohort from the typed FORMAT/PL vector of a diploid record (int8 / int16 / int32,
+        n * A (A + 1) / 2 values), decoded on the device to the effect allele's expected count (nps_cohort_push_pl); the
+        descriptors that score the row carry RIE_COUNTS_EFFECT"""
+        pl = _pl_vector(pl, self.n_samples, n_alleles)
+        _check(load().nps_cohort_push_pl(self._h, int(row), pl.ctypes.data, pl.dtype.itemsize, int(n_alleles), int(eaidx)))
 
     def convert_from(self, src: "Cohort"):
         """fill this FMT_GT2M cohort (and its row tallies) from a FMT_GT2 cohort of the same shape"""
@@ -418,6 +445,12 @@ class Scorer:
             raise ValueError("ds has %d values, expected %d" % (ds.size, self.n))
         _check(load().nps_push_ds(self._h, ds.ctypes.data, int(bool(ref_is_effect)), float(beta),
                                   float(eaf)))
+
+    def push_pl(self, pl: np.ndarray, n_alleles: int, eaidx: int, ref_is_effect, beta: float, eaf: float):
+        """FORMAT/PL of a diploid record: int8 / int16 / int32 array of n * A (A + 1) / 2 values (nps_push_pl)"""
+        pl = _pl_vector(pl, self.n, n_alleles)
+        _check(load().nps_push_pl(self._h, pl.ctypes.data, pl.dtype.itemsize, int(n_alleles), int(eaidx),
+                                  int(bool(ref_is_effect)), float(beta), float(eaf)))
 
     def push_packed(self, row: np.ndarray, ref_is_effect, beta: float, eaf: float):
         row = np.ascontiguousarray(row, dtype=np.uint32)

@@ -204,6 +204,32 @@ long nh_vcf_find_ds(void *h, const char *contig, long pos, const char *ref, cons
     return n;
 }
 
+// the FORMAT/PL row the score loop would score for this score row (decodePlDosage of the record's vector, the host mirror of
+// the device decode): returns the number of values written (= samples), 0 when the record found is not scored from PL
+// (NIMPRESS_FORMAT=PL unset, no PL, or more than 8 alleles), -1 when no record matches, -2 on error (nh_last_error)
+long nh_vcf_find_pl(void *h, const char *contig, long pos, const char *ref, const char *ea, float *out, long cap) {
+    try {
+        const VCF &vcf = ((nh_vcf *)h)->vcf;
+        const Variant *v = findVariant(contig, pos, ref, ea, vcf);
+        if (!v) return -1;
+        if (!v->has_pl) return 0;
+        int eaidx = 0;
+        if (std::string(ref) != ea) {
+            eaidx = -1;
+            for (size_t k = 0; k < v->alt.size(); ++k)
+                if (v->alt[k] == ea) eaidx = (int)k + 1;
+        }
+        std::vector<float> row(vcf.samples.size());
+        decodePlDosage(v->pl_raw.data(), v->pl_bytes, row.size(), 1 + (int)v->alt.size(), eaidx, row.data());
+        const long n = std::min<long>((long)row.size(), cap);
+        if (n > 0) memcpy(out, row.data(), sizeof(float) * (size_t)n);
+        return n;
+    } catch (const std::exception &ex) {
+        g_nh_error = ex.what();
+        return -2;
+    }
+}
+
 // The row classifier both scoring drivers call (classifyRow), for every row of a score file against a genotype file
 // opened with the score loci kept, with an optional coverage BED: kind (0 = genotyped, else nps_row_kind), eaidx,
 // ref_is_effect and code map per row (cap ints each), the FILTER strings of the rows '\n'-joined.  Returns the
@@ -494,6 +520,19 @@ long nh_compute_multi_ex(const char *score_paths, const char *vcf_path, const ch
 long nh_decode_gt_dosage(const void *gts, int elem_bytes, long n, int ploidy, int eaidx, float *out) {
     if (!gts || !out || n < 0 || ploidy < 1 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)) return -1;
     decodeGtDosage(gts, elem_bytes, (size_t)n, ploidy, eaidx, out);
+    return n;
+}
+// the host's decode of a typed FORMAT/PL vector (decodePlDosage): n values written, -1 on bad arguments
+long nh_decode_pl_dosage(const void *pl, int elem_bytes, long n, int n_alleles, int eaidx, float *out) {
+    if (!pl || !out || n < 0 || n_alleles < 2 || n_alleles > 8 || eaidx < 0 || eaidx >= n_alleles ||
+        (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
+        return -1;
+    try {
+        decodePlDosage(pl, elem_bytes, (size_t)n, n_alleles, eaidx, out);
+    } catch (const std::exception &ex) {
+        g_nh_error = ex.what();
+        return -1;
+    }
     return n;
 }
 long nh_decode_code_dosage(const unsigned char *codes, long n, int code_map, float *out) {

@@ -79,6 +79,18 @@ struct Variant {
     // the dosage row the loop scores for effect allele index eaidx (0 = REF: the sum of the ALT dosages, which
     // nps_push_ds turns into 2 - sum; k = ALT[k-1]): `tmp` is used unless the record's own vector can be handed over
     const float *dsRow(int eaidx, size_t n_samples, std::vector<float> &tmp) const;
+    // FORMAT/PL (build-defined extension, parity unpinned: the reference decodes GT only): the phred-scaled genotype
+    // likelihoods of diploid samples, pl_per_sample = A (A + 1) / 2 values per sample for the record's A = 1 + alt.size()
+    // alleles, in the order of the VCF specification.  Kept ONLY under NIMPRESS_FORMAT=PL, for a record that carries PL
+    // and has 2 .. 8 alleles: the record is then scored from PL (nps_push_pl: the effect allele's expected count under a
+    // flat genotype prior) and neither its GT nor its DS is kept.  pl_raw: BCF -> the record's typed vector as it stands
+    // (int8 / int16 / int32, pl_bytes = 1 / 2 / 4), never widened; text VCF -> int32 values (pl_bytes = 4), a missing
+    // value 0x80000000, a short vector padded with the end-of-vector value 0x80000001, a value beyond int32 held as
+    // INT32_MAX (the decode caps at 255).
+    bool has_pl = false;
+    int pl_per_sample = 0;
+    int pl_bytes = 4;
+    std::vector<uint8_t> pl_raw;
     // PLINK 1 .bed source (build-defined extension): gt_raw holds the variant's ceil(N/4) .bed bytes,
     // ref = A2 and alt = {A1} of the .bim line.  A .bim has no notion of REF, so findVariant also
     // accepts a score row whose ref is A1.
@@ -201,7 +213,9 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
 // nps_cohort_upload and scored in two reads for all files (nps_score_cohort_multi on a dosage cohort).  A position whose
 // record is scored from GT (or from .bed / .pgen codes) is decoded on the host to the float32 row of its effect
 // allele's counts and flagged NPS_RIE_COUNTS_EFFECT; warnings come from nps_multi_row_tallies, the same bits the
-// file-by-file path sees.  A block without a FORMAT/DS position takes the 2-bit route unchanged.
+// file-by-file path sees.  A block without a FORMAT/DS position takes the 2-bit route unchanged.  A record scored from
+// FORMAT/PL (NIMPRESS_FORMAT=PL) is a dosage position too: its row is filled on the host (decodePlDosage, the mirror of
+// the device decode) and flagged NPS_RIE_COUNTS_EFFECT; without acceptDs it is refused like a FORMAT/DS record.
 // shard / n_shards / partial: the rows-sharded x all-scores layout over several GPUs.  The
 // union's rows are cut into n_shards contiguous blocks; this call locates, decodes and scores block `shard` only
 // (1 / n_shards of the ingest and of the cohort) for ALL files, and with partial = true returns the state of the

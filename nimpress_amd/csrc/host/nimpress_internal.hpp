@@ -45,6 +45,13 @@ void writeRowWarnings(Log &log, const ScoreEntry &e, int kind, const std::string
 void decodeGtDosage(const void *gts, int elem_bytes, size_t n, int ploidy, int eaidx, float *out);
 // the same for the 2-bit codes of a .bed / .pgen record under its code map (NPS_MAP_*)
 void decodeCodeDosage(const uint8_t *codes, size_t n, int code_map, float *out);
+// The host mirror of decode_pl_kernel (include/nps.h above nps_push_pl: same table -- nps_pl_likelihoods --, same order,
+// same rules), for the one-pass dosage route and the CPU tests.  pl: the typed FORMAT/PL vector (elem_bytes 1 / 2 / 4) of n
+// diploid samples, G = A (A + 1) / 2 values each for A = n_alleles (2 .. 8), genotype (j, k), j <= k, at k (k + 1) / 2 + j.
+// Per sample: NaN when any value is negative (missing, end of vector) or the vector is flat; else with
+// w_g = T[min(PL_g, 255)] the float32 of sum_g ((j == eaidx) + (k == eaidx)) w_g / sum_g w_g, both sums float64 in
+// ascending g.
+void decodePlDosage(const void *pl, int elem_bytes, size_t n, int n_alleles, int eaidx, float *out);
 
 }  // namespace nimpress
 #pragma GCC visibility pop

@@ -125,6 +125,71 @@ static int encodeGT(const char *p, const char *end, int32_t *out, int cap) {
     return n;
 }
 
+// FORMAT/PL instead of GT / DS for records that carry it and have 2 .. 8 alleles: NIMPRESS_FORMAT=PL (opt-in only: with
+// the variable unset or DS, PL is ignored)
+static bool preferPL() {
+    const char *e = getenv("NIMPRESS_FORMAT");
+    return e && (strcmp(e, "PL") == 0 || strcmp(e, "pl") == 0);
+}
+static const int32_t kPlMissing = (int32_t)0x80000000u;
+
+// The FORMAT/PL subfields (index pli) of the ns sample columns starting at s -> v.pl_raw as int32, G = A (A + 1) / 2 values
+// per sample, parsed in place.  "." or an empty field makes the whole sample missing (a "." inside a list that one value);
+// a short vector is padded with the end-of-vector value; a value beyond int32 is held as INT32_MAX (the decode caps at
+// 255); a non-integer and a vector longer than G are errors naming the record.
+static void parseTextPl(const char *s, const char *end, size_t ns, int pli, int n_alleles, Variant &v) {
+    const int G = n_alleles * (n_alleles + 1) / 2;
+    const std::string at = v.contig + ":" + std::to_string(v.pos);
+    v.has_gt = false;
+    v.has_ds = false;
+    v.has_pl = true;
+    v.pl_per_sample = G;
+    v.pl_bytes = 4;
+    std::vector<int32_t> vals(ns * (size_t)G);
+    int32_t *dst = vals.data();
+    for (size_t i = 0; i < ns; ++i, dst += G) {
+        const char *t = s;
+        while (t < end && *t != '\t') ++t;
+        const char *g0 = s;  // pli-th ':' separated subfield of [s, t)
+        for (int k = 0; k < pli && g0 < t; ++k) {
+            while (g0 < t && *g0 != ':') ++g0;
+            if (g0 < t) ++g0;
+        }
+        const char *g1 = g0;
+        while (g1 < t && *g1 != ':') ++g1;
+        for (int k = 0; k < G; ++k) dst[k] = kVectorEnd;
+        if (g0 == g1 || (g1 - g0 == 1 && *g0 == '.')) {
+            for (int k = 0; k < G; ++k) dst[k] = kPlMissing;
+        } else {
+            const char *a = g0;
+            for (int k = 0;; ++k) {
+                const char *b = a;
+                while (b < g1 && *b != ',') ++b;
+                if (k >= G)
+                    throw std::runtime_error("FORMAT/PL with more than " + std::to_string(G) + " values (" +
+                                             std::to_string(n_alleles) + " alleles) at " + at);
+                if (b == a || (b - a == 1 && *a == '.')) {
+                    dst[k] = kPlMissing;
+                } else {
+                    int64_t x = 0;
+                    for (const char *c = a; c < b; ++c) {
+                        if (*c < '0' || *c > '9')
+                            throw std::runtime_error("bad FORMAT/PL value '" + std::string(a, (size_t)(b - a)) + "' at " + at);
+                        if (x <= INT32_MAX) x = x * 10 + (*c - '0');
+                    }
+                    dst[k] = x > INT32_MAX ? INT32_MAX : (int32_t)x;
+                }
+                if (b >= g1) break;
+                a = b + 1;
+            }
+        }
+        if (t >= end && i + 1 < ns) throw std::runtime_error("VCF record with too few sample columns");
+        s = t + 1;
+    }
+    v.pl_raw.resize(vals.size() * sizeof(int32_t));
+    if (!vals.empty()) memcpy(v.pl_raw.data(), vals.data(), v.pl_raw.size());
+}
+
 // One VCF data line -> Variant.  `wanted` (optional): keep only records overlapping one of its
 // regions; returns false when the record is filtered out.
 typedef std::unordered_map<std::string, std::vector<std::pair<int64_t, int64_t>>> RegionMap;
@@ -173,6 +238,20 @@ static bool parseRecordLine(const char *L, size_t len, size_t ns, const RegionMa
         for (size_t k = 0; k < fmt.size(); ++k) {
             if (fmt[k] == "GT") gi = (int)k;
             if (fmt[k] == "DS") di = (int)k;
+        }
+        int pli = -1;
+        if (preferPL())
+            for (size_t k = 0; k < fmt.size(); ++k)
+                if (fmt[k] == "PL") pli = (int)k;
+        if (pli >= 0) {  // NIMPRESS_FORMAT=PL: a record that carries PL and has 2 .. 8 alleles is scored from it
+            const int n_alleles = 1 + (int)v.alt.size();
+            if (n_alleles >= 2 && n_alleles <= 8) {
+                parseTextPl(col[9], end, ns, pli, n_alleles, v);
+                return true;
+            }
+            if (n_alleles > 8 && gi < 0 && di < 0)
+                throw std::runtime_error("FORMAT/PL of a record with " + std::to_string(n_alleles) +
+                                         " alleles (at most 8) and no FORMAT/GT or FORMAT/DS at " + v.contig + ":" + field(1));
         }
         if (gi < 0 && di < 0)
             throw std::runtime_error("VCF record without FORMAT/GT (or FORMAT/DS) at " + v.contig + ":" + field(1));
@@ -741,6 +820,14 @@ static bool parseBcfRecord(const unsigned char *shared, size_t l_shared, const u
     int64_t ds_len = 0;
     const unsigned char *ds_ptr = nullptr;
     size_t ds_bytes = 0;
+    const unsigned char *gt_ptr = nullptr;
+    size_t gt_nbytes = 0;
+    const bool prefer_pl = preferPL();
+    bool has_pl = false;
+    int pl_type = 0;
+    int64_t pl_len = 0;
+    const unsigned char *pl_ptr = nullptr;
+    size_t pl_bytes = 0;
     for (uint32_t k = 0; k < n_fmt; ++k) {
         const int32_t key = f.typedInt();
         int type;
@@ -753,7 +840,8 @@ static bool parseBcfRecord(const unsigned char *shared, size_t l_shared, const u
             if (len > 8) throw std::runtime_error("ploidy above 8 is not supported");
             v.ploidy = (int)len;
             v.gt_bytes = type == 1 ? 1 : (type == 2 ? 2 : 4);
-            v.gt_raw.assign(f.p, f.p + bytes);
+            gt_ptr = f.p;  // copied below, and only when the record is scored from its GT
+            gt_nbytes = bytes;
             v.has_gt = true;
         } else if (key >= 0 && (size_t)key < h.ids.size() && h.ids[(size_t)key] == "DS") {
             // remembered only: whether the record is scored from GT or from DS is decided below, and a DS that is not
@@ -763,8 +851,36 @@ static bool parseBcfRecord(const unsigned char *shared, size_t l_shared, const u
             ds_ptr = f.p;
             ds_bytes = bytes;
             v.has_ds = true;
+        } else if (prefer_pl && key >= 0 && (size_t)key < h.ids.size() && h.ids[(size_t)key] == "PL") {
+            // remembered like DS: validated and copied only when the record is scored from it
+            pl_type = type;
+            pl_len = len;
+            pl_ptr = f.p;
+            pl_bytes = bytes;
+            has_pl = true;
         }
         f.p += bytes;
+    }
+    if (has_pl && n_sample) {  // NIMPRESS_FORMAT=PL: a record that carries PL and has 2 .. 8 alleles is scored from it
+        const int64_t n_alleles = 1 + (int64_t)v.alt.size();
+        const std::string at = v.contig + ":" + std::to_string(v.pos);
+        if (n_alleles >= 2 && n_alleles <= 8) {
+            if (pl_type < 1 || pl_type > 3) throw std::runtime_error("BCF: FORMAT/PL is not an int8, int16 or int32 vector at " + at);
+            if (pl_len != n_alleles * (n_alleles + 1) / 2)
+                throw std::runtime_error("BCF: FORMAT/PL holds " + std::to_string(pl_len) + " values per sample, " +
+                                         std::to_string(n_alleles * (n_alleles + 1) / 2) + " expected for " +
+                                         std::to_string(n_alleles) + " alleles at " + at);
+            v.has_pl = true;
+            v.pl_per_sample = (int)pl_len;
+            v.pl_bytes = pl_type == 1 ? 1 : (pl_type == 2 ? 2 : 4);
+            v.pl_raw.assign(pl_ptr, pl_ptr + pl_bytes);
+            v.has_gt = false;
+            v.has_ds = false;
+            return true;
+        }
+        if (n_alleles > 8 && !v.has_gt && !v.has_ds)
+            throw std::runtime_error("FORMAT/PL of a record with " + std::to_string(n_alleles) +
+                                     " alleles (at most 8) and no FORMAT/GT or FORMAT/DS at " + at);
     }
     if (n_sample && !v.has_gt && !v.has_ds)
         throw std::runtime_error("BCF record without FORMAT/GT (or FORMAT/DS) at " + v.contig + ":" + std::to_string(v.pos));
@@ -780,10 +896,9 @@ static bool parseBcfRecord(const unsigned char *shared, size_t l_shared, const u
                 throw std::runtime_error("FORMAT/DS value " + std::to_string(x) + " is not finite at " + v.contig + ":" +
                                          std::to_string(v.pos));
         v.has_gt = false;
-        v.gt_raw.clear();
-        v.gt_raw.shrink_to_fit();
     } else {
         v.has_ds = false;
+        if (v.has_gt) v.gt_raw.assign(gt_ptr, gt_ptr + gt_nbytes);
     }
     return true;
 }

@@ -209,6 +209,46 @@ void decodeGtDosage(const void *gts, int elem_bytes, size_t n, int ploidy, int e
     default: throw std::runtime_error("decodeGtDosage: FORMAT/GT elements of " + std::to_string(elem_bytes) + " bytes");
     }
 }
+template <class T>
+static void plDosageRow(const T *p, size_t n, int n_alleles, int eaidx, const double *lik, float *out) {
+    const int G = n_alleles * (n_alleles + 1) / 2;
+    for (size_t i = 0; i < n; ++i, p += G) {
+        double num = 0.0, den = 0.0;
+        int32_t lo = INT32_MAX, hi = INT32_MIN;
+        int j = 0, k = 0;  // genotype g = (j, k), j <= k
+        for (int g = 0; g < G; ++g) {
+            const int32_t v = (int32_t)p[g];
+            lo = std::min(lo, v);
+            hi = std::max(hi, v);
+            const double w = lik[v < 0 ? 0 : (v > 255 ? 255 : v)];
+            const int cnt = (j == eaidx) + (k == eaidx);
+            num = num + (double)cnt * w;
+            den = den + w;
+            if (j == k) {
+                j = 0;
+                ++k;
+            } else {
+                ++j;
+            }
+        }
+        out[i] = (lo < 0 || lo == hi) ? std::nanf("") : (float)(num / den);
+    }
+}
+void decodePlDosage(const void *pl, int elem_bytes, size_t n, int n_alleles, int eaidx, float *out) {
+    if (n_alleles < 2 || n_alleles > 8 || eaidx < 0 || eaidx >= n_alleles)
+        throw std::runtime_error("decodePlDosage: " + std::to_string(n_alleles) + " alleles, effect allele " + std::to_string(eaidx));
+    static const std::vector<double> lik = [] {  // the table libnps built (and uploads): nps_pl_likelihoods
+        std::vector<double> t(256);
+        npsCheck(nps_pl_likelihoods(t.data()), "nps_pl_likelihoods");
+        return t;
+    }();
+    switch (elem_bytes) {
+    case 1: plDosageRow((const int8_t *)pl, n, n_alleles, eaidx, lik.data(), out); break;
+    case 2: plDosageRow((const int16_t *)pl, n, n_alleles, eaidx, lik.data(), out); break;
+    case 4: plDosageRow((const int32_t *)pl, n, n_alleles, eaidx, lik.data(), out); break;
+    default: throw std::runtime_error("decodePlDosage: FORMAT/PL elements of " + std::to_string(elem_bytes) + " bytes");
+    }
+}
 void decodeCodeDosage(const uint8_t *codes, size_t n, int code_map, float *out) {
     // .bed: 0 = hom A1, 1 = missing, 2 = het, 3 = hom A2; .pgen: the number of ALT alleles, 3 = missing
     static const float nanv = std::nanf("");
@@ -266,6 +306,10 @@ void computePolygenicScores(std::vector<double> &scores, const ScoreFile &scoreF
             const int rie = c.ref_is_effect, eaidx = c.eaidx;
             if (c.kind)  // nim:526-558: a constant row, no genotypes
                 npsCheck(nps_push_locus(ctx, c.kind, rie, e.beta, e.eaf), "nps_push_locus");
+            else if (v->has_pl)  // FORMAT/PL row (build-defined, NIMPRESS_FORMAT=PL): the effect allele's expected count,
+                                 // decoded on the device; statistics and warnings as for a FORMAT/DS row
+                npsCheck(nps_push_pl(ctx, v->pl_raw.data(), v->pl_bytes, 1 + (int)v->alt.size(), eaidx, rie, e.beta, e.eaf),
+                         "nps_push_pl");
             else if (v->has_ds)  // FORMAT/DS row (build-defined; the seam of nim:381-391 for float dosages)
                 npsCheck(nps_push_ds(ctx, v->dsRow(eaidx, (size_t)nsamples, ds_tmp), rie, e.beta, e.eaf),
                          "nps_push_ds");
@@ -386,7 +430,10 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
                 Tick tick(timings().push);
                 if (as_ds) {
                     float *row = rows.data() + (j - w0) * (size_t)nsamples;
-                    if (v->has_ds) {
+                    if (v->has_pl) {  // the effect allele's expected count: the row counts the effect allele, like a GT row
+                        from_gt[j] = 1;
+                        decodePlDosage(v->pl_raw.data(), v->pl_bytes, (size_t)nsamples, 1 + (int)v->alt.size(), c.eaidx, row);
+                    } else if (v->has_ds) {
                         memcpy(row, v->dsRow(c.eaidx, (size_t)nsamples, ds_tmp), sizeof(float) * (size_t)nsamples);
                     } else {
                         from_gt[j] = 1;
@@ -397,8 +444,10 @@ void computePolygenicScoresMulti(std::vector<std::vector<double>> &scores, const
                     }
                     continue;
                 }
-                if (v->has_ds) {
-                    if (!acceptDs) throw std::runtime_error("FORMAT/DS records are not covered by the one-pass multi-score path");
+                if (v->has_ds || v->has_pl) {  // (a FORMAT/PL record is a dosage row too)
+                    if (!acceptDs)
+                        throw std::runtime_error(std::string(v->has_pl ? "FORMAT/PL" : "FORMAT/DS") +
+                                                 " records are not covered by the one-pass multi-score path");
                     again = true;  // the block holds dosages: fill a float32 cohort from its first row on
                     break;
                 }

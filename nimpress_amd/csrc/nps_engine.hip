@@ -193,6 +193,7 @@ struct nps_ctx {
     DevBuf<DsRowP> d_rds_rowp;
 
     StagingRing poly{2};  // raw GT records of ploidy > 2, read by the decode kernel (grows to the widest record pushed)
+    StagingRing pl{4};    // FORMAT/PL vectors of nps_push_pl, read by decode_pl_kernel (grows to the widest record pushed)
 
     // accumulators
     AccumGeom geom{};         // streaming geometry (groups_per_chunk for a full batch)
@@ -635,6 +636,49 @@ static int push_gt_polyploid(nps_ctx *c, const void *gts, int elem_bytes, int pl
             ProfScope ps(c, P_DECODE);
             HIP_TRY(launch_decode_gt_to_ds(c->stream.get(), s, elem_bytes, c->n, ploidy, eaidx,
                                            c->d_ds.get() + (uint64_t)slot * c->ds_stride_f));
+            return NPS_OK;
+        });
+        if (rc) return rc;
+    }
+    commit_data_row(c, c->ds, slot);
+    return NPS_OK;
+}
+
+// the typed FORMAT/PL vector of a diploid record with n_alleles alleles (REF + ALTs)
+static int check_raw_pl(int elem_bytes, int n_alleles, int eaidx) {
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
+        return fail(NPS_E_INVAL, "elem_bytes %d (1, 2 or 4)", elem_bytes);
+    if (n_alleles < 2 || n_alleles > 8) return fail(NPS_E_UNSUPPORTED, "FORMAT/PL of %d alleles (2 .. 8)", n_alleles);
+    if (eaidx < 0 || eaidx >= n_alleles) return fail(NPS_E_INVAL, "eaidx %d outside the %d alleles", eaidx, n_alleles);
+    return NPS_OK;
+}
+
+extern "C" int nps_pl_likelihoods(double *out256) {
+    if (!out256) return fail(NPS_E_INVAL, "out256 is NULL");
+    memcpy(out256, pl_likelihood_table(), 256 * sizeof(double));
+    return NPS_OK;
+}
+
+// PRESENT row with FORMAT/PL (build-defined, include/nps.h): like a polyploid GT record, the vector is decoded on the
+// device into a float dosage row that already counts the effect allele, and scored through the DS path
+extern "C" int nps_push_pl(nps_ctx *c, const void *pl, int elem_bytes, int n_alleles, int eaidx, int ref_is_effect,
+                           double beta, double eaf) {
+    if (int urc = check_usable(c)) return urc;
+    if (int arc = check_raw_pl(elem_bytes, n_alleles, eaidx)) return arc;
+    if (c->n && !pl) return fail(NPS_E_INVAL, "pl is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_ds(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)elem_bytes * (size_t)(n_alleles * (n_alleles + 1) / 2) * c->n;
+    if (c->n) HIP_TRY(c->pl.ensure(pl_slot_bytes(bytes), c->stream.get()));  // (rare: once or twice per context)
+    uint32_t slot;
+    rc = begin_data_row(c, c->ds, ref_is_effect, NPS_RIE_COUNTS_EFFECT, beta, eaf, &slot);
+    if (rc) return rc;
+    if (c->n) {
+        rc = stage_row(c->pl, c->stream.get(), [&](void *s) { memcpy(s, pl, bytes); }, [&](void *s) -> int {
+            ProfScope ps(c, P_DECODE);
+            HIP_TRY(launch_decode_pl(c->stream.get(), s, elem_bytes, c->n, n_alleles, eaidx,
+                                     c->d_ds.get() + (uint64_t)slot * c->ds_stride_f));
             return NPS_OK;
         });
         if (rc) return rc;
@@ -1131,9 +1175,12 @@ extern "C" int nps_cohort_upload_bed(nps_cohort *c, uint64_t row0, uint64_t nrow
 
 // one row of a NPS_FMT_GT2 cohort from the buffer a VCF/BCF record holds, decoded on the device (the resident form of
 // nps_push_gt_raw / nps_push_bed: same kernels, the cohort is the destination)
-static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes) {
+// (format: what the pushed row decodes to -- 2-bit codes, or for nps_cohort_push_pl float32 dosages)
+static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes, int format = NPS_FMT_GT2) {
     if (!c) return fail(NPS_E_INVAL, "cohort is NULL");
-    if (c->format != NPS_FMT_GT2) return fail(NPS_E_UNSUPPORTED, "rows are pushed into NPS_FMT_GT2 cohorts only");
+    if (c->format != format)
+        return format == NPS_FMT_GT2 ? fail(NPS_E_UNSUPPORTED, "rows are pushed into NPS_FMT_GT2 cohorts only")
+                                     : fail(NPS_E_UNSUPPORTED, "FORMAT/PL rows are pushed into NPS_FMT_DS32 cohorts only");
     if (row >= c->n_rows) return fail(NPS_E_INVAL, "row %llu outside cohort of %llu rows", (unsigned long long)row,
                                       (unsigned long long)c->n_rows);
     HIP_TRY(hipSetDevice(c->device));
@@ -1143,7 +1190,7 @@ static int cohort_push_prepare(nps_cohort *c, uint64_t row, size_t bytes) {
         if (rc) return rc;
         HIP_TRY(c->push_stream.create());
     }
-    if (!c->d_push_tally.get()) HIP_TRY(c->d_push_tally.alloc(256 / sizeof(unsigned long long)));
+    if (format == NPS_FMT_GT2 && !c->d_push_tally.get()) HIP_TRY(c->d_push_tally.alloc(256 / sizeof(unsigned long long)));
     if (c->optimized) {
         HIP_TRY(hipDeviceSynchronize());
         int rc = cohort_unoptimize(c);
@@ -1181,6 +1228,22 @@ extern "C" int nps_cohort_push_bed(nps_cohort *c, uint64_t row, const uint8_t *b
         HIP_TRY(launch_tally_scatter_row(c->push_stream.get(), (const uint32_t *)s, c->n_samples, effect_is_a1,
                                          (uint32_t *)c->d_data.get() + (row >> 2) * sw * 4, (int)(row & 3),
                                          c->d_push_tally.get()));
+        return NPS_OK;
+    });
+}
+
+// One row of a NPS_FMT_DS32 cohort from the FORMAT/PL vector of a record (the resident form of nps_push_pl: same kernel,
+// the cohort is the destination).  The values written are in [0, 2] or NaN: the cohort's out-of-range state is untouched.
+extern "C" int nps_cohort_push_pl(nps_cohort *c, uint64_t row, const void *pl, int elem_bytes, int n_alleles, int eaidx) {
+    if (int arc = check_raw_pl(elem_bytes, n_alleles, eaidx)) return arc;
+    if (c && c->n_samples && !pl) return fail(NPS_E_INVAL, "pl is NULL");
+    const size_t bytes = c ? (size_t)elem_bytes * (size_t)(n_alleles * (n_alleles + 1) / 2) * c->n_samples : 0;
+    int rc = cohort_push_prepare(c, row, std::max<size_t>(pl_slot_bytes(bytes), 16), NPS_FMT_DS32);
+    if (rc) return rc;
+    if (c->n_samples == 0) return NPS_OK;
+    return stage_row(c->push, c->push_stream.get(), [&](void *s) { memcpy(s, pl, bytes); }, [&](void *s) -> int {
+        HIP_TRY(launch_decode_pl(c->push_stream.get(), s, elem_bytes, c->n_samples, n_alleles, eaidx,
+                                 (float *)(c->d_data.get() + row * c->stride_bytes)));
         return NPS_OK;
     });
 }
@@ -2394,7 +2457,11 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
     if (rc) return rc;
     if (def->n_desc == 0) return NPS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    if (is_ds) return multi_score_ds(m, co, cohort_row0, def);
+    if (is_ds) {
+        rc = cohort_quiesce(co);  // rows pushed into the cohort (nps_cohort_push_pl) are complete
+        if (rc) return rc;
+        return multi_score_ds(m, co, cohort_row0, def);
+    }
     const MultiPlan pl = multi_plan(m->n, def->n_desc, m->S, def->ND, m->coarse_missing, m->cus);
     HIP_TRY(m->d_table.ensure(pl.table_bytes() + pl.flag_bytes(), m->stream.get()));
     HIP_TRY(m->d_partial.ensure(pl.partial_elems(), m->stream.get()));

@@ -196,6 +196,14 @@ hipError_t launch_ds_range_check(hipStream_t st, const float *d_ds, uint64_t str
                                  unsigned char *d_bad);
 hipError_t launch_decode_gt_to_ds(hipStream_t st, const void *d_gts, int elem_bytes, uint64_t n,
                                   int ploidy, int eaidx, float *d_out);
+// FORMAT/PL of a diploid record (nps_pl.hip; the arithmetic: include/nps.h above nps_push_pl) -> the float32 row of the
+// effect allele's expected count.  src: n x A (A + 1) / 2 values of elem_bytes in PINNED HOST memory, 16-byte aligned and
+// readable up to the next multiple of 16 bytes past its end (pl_slot_bytes); 2 <= n_alleles <= 8, 0 <= eaidx < n_alleles.
+hipError_t launch_decode_pl(hipStream_t st, const void *src, int elem_bytes, uint64_t n, int n_alleles, int eaidx,
+                            float *d_out);
+static inline size_t pl_slot_bytes(size_t row_bytes) { return (row_bytes + 15) / 16 * 16; }
+// the 256 likelihoods T[k] = 10^(-k/10) the kernel uses (built once, on the host)
+const double *pl_likelihood_table();
 hipError_t launch_synth_ds(hipStream_t st, float *d_ds, uint64_t stride_f, uint64_t n, uint64_t row0,
                            uint64_t gen_row0, uint64_t n_rows, uint64_t seed, const uint32_t *d_t_het,
                            const uint32_t *d_t_hom, const uint32_t *d_t_miss);

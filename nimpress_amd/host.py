@@ -50,6 +50,10 @@ def load():
         L.nh_decode_gt_dosage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
         L.nh_decode_code_dosage.restype = C.c_long
         L.nh_decode_code_dosage.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+        L.nh_decode_pl_dosage.restype = C.c_long
+        L.nh_decode_pl_dosage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+        L.nh_vcf_find_pl.restype = C.c_long
+        L.nh_vcf_find_pl.argtypes = [C.c_void_p, C.c_char_p, C.c_long, C.c_char_p, C.c_char_p, C.c_void_p, C.c_long]
         L.nh_last_log_size.restype = C.c_long
         L.nh_last_log.restype = C.c_long
         L.nh_last_log.argtypes = [C.c_char_p, C.c_long]
@@ -111,6 +115,57 @@ def decode_code_dosage(codes: np.ndarray, n: int, code_map: int) -> np.ndarray:
     if load().nh_decode_code_dosage(codes.ctypes.data, int(n), int(code_map), out.ctypes.data) < 0:
         raise capi.NpsError(-1, "nh_decode_code_dosage: bad arguments")
     return out[:n]
+
+
+def decode_pl_dosage(pl: np.ndarray, n_alleles: int, eaidx: int) -> np.ndarray:
+    """the host's decode of a typed FORMAT/PL vector (int8 / int16 / int32, n x A (A + 1) / 2 values of n diploid samples at
+    a record of A = n_alleles alleles) into the float32 row of the effect allele's expected count -- the mirror of the
+    device decode of nps_push_pl (include/nps.h): NaN = a missing or uninformative sample"""
+    pl = np.ascontiguousarray(pl)
+    G = n_alleles * (n_alleles + 1) // 2
+    if pl.dtype not in (np.int8, np.int16, np.int32) or G < 1 or pl.size % G:
+        raise ValueError("pl must be int8 / int16 / int32 with n * A (A + 1) / 2 values")
+    out = np.empty(max(pl.size // G, 1), dtype=np.float32)
+    n = load().nh_decode_pl_dosage(pl.ctypes.data, pl.dtype.itemsize, pl.size // G, int(n_alleles), int(eaidx), out.ctypes.data)
+    if n < 0:
+        raise capi.NpsError(-1, "nh_decode_pl_dosage: bad arguments")
+    return out[:n]
+
+
+class GenotypeFile:
+    """a genotype file opened by the host's reader (nh_vcf_open), records kept -- for looking at what the score loop would
+    see of a record.  score_path: keep only the records of that score file's loci."""
+
+    def __init__(self, path: str, score_path: Optional[str] = None):
+        self._h = load().nh_vcf_open(path.encode(), score_path.encode() if score_path else None)
+        if not self._h:
+            raise capi.NpsError(-1, "cannot open %s: %s" % (path, load().nh_last_error().decode("utf-8", "replace")))
+        self.n_samples = int(load().nh_vcf_n_samples(self._h))
+
+    def find_pl(self, contig: str, pos: int, ref: str, ea: str) -> Optional[np.ndarray]:
+        """the FORMAT/PL dosage row of the record a score row selects (nh_vcf_find_pl): float32[n_samples]; None when the
+        record found is not scored from PL (NIMPRESS_FORMAT=PL not set when the file was opened, no PL, more than 8
+        alleles); KeyError when no record matches"""
+        out = np.empty(max(self.n_samples, 1), dtype=np.float32)
+        n = load().nh_vcf_find_pl(self._h, contig.encode(), int(pos), ref.encode(), ea.encode(), out.ctypes.data, self.n_samples)
+        if n == -1:
+            raise KeyError("%s:%d:%s:%s" % (contig, pos, ref, ea))
+        if n < 0:
+            raise capi.NpsError(-1, load().nh_last_error().decode("utf-8", "replace"))
+        if n == 0 and self.n_samples:
+            return None
+        return out[:n]
+
+    def close(self):
+        if self._h:
+            load().nh_vcf_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 TIMING_KEYS = ("hip_init_s", "hip_init_wait_s", "open_s", "inflate_parse_s", "push_s", "kernel_s", "warnings_s")
