@@ -395,6 +395,51 @@ void nps_scoredef_destroy(nps_scoredef *d);
 int nps_score_cohort_def(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0,
                          const nps_scoredef *def, int mode);
 
+/* ---- a chosen subset of a resident cohort's samples ----------------------------------------
+ * One ancestry group, cases against controls, the unrelated samples, a batch: scored as `plink --keep` or `bcftools -s`
+ * followed by the reference would score them -- the group as if it were the whole file -- without a second copy of the
+ * matrix.  (Build-defined extension: the reference scores the samples of the file it is given, nimpress.nim:626-628.)
+ *
+ * A sample set is a mask over the samples of a cohort: keep[i] == 0 drops sample i, anything else keeps it.  Immutable
+ * after creation; contexts on several threads may share one; it counts in nps_live_resources.  NPS_E_INVAL: keep == NULL,
+ * n_samples == 0, no sample kept. */
+typedef struct nps_sampleset nps_sampleset;
+int nps_sampleset_create(nps_sampleset **out, int device, uint64_t n_samples, const uint8_t *keep /* [n_samples], host */);
+uint64_t nps_sampleset_n_samples(const nps_sampleset *s);
+uint64_t nps_sampleset_n_kept(const nps_sampleset *s);
+void nps_sampleset_destroy(nps_sampleset *s);
+/* The run is nps_score_cohort_def on the cohort that holds only the kept samples' columns:
+ *   tallyAlleles        nimpress.nim:32-47   of every PRESENT row counts the kept samples only;
+ *   the --maxmis test   nimpress.nim:565     is nmissing_kept / n_kept > rate;
+ *   ngenotyped          = n_kept - nmissing_kept enters --mincs (nimpress.nim:471) and the cohort-frequency imputation value
+ *                       neffect_kept / ngenotyped (:472);
+ *   nps_flush           returns these per-row statistics -- for 2-bit rows bit-exact; on a NPS_FMT_DS32 row neffect is the
+ *                       float64 sum over the kept non-missing samples, added in the fixed tree of the whole-cohort tally with
+ *                       the dropped samples' terms left out (every sample kept: the bits of nps_score_cohort_def under
+ *                       NPS_MODE_TWOPASS);
+ *   rows without data   (UNCOVERED / ABSENT / FILTERED, nimpress.nim:526-558) behave as in nps_score_cohort_def.
+ * The context is the cohort's: created for the cohort's n_samples, its layout and accumulation grid are the cohort's, and
+ * the run reads the matrix twice (a tally pass under the mask, then the accumulation of NPS_MODE_TWOPASS); the tallies are
+ * counted again on every call, into the context -- tallies kept with the cohort (nps_cohort_keep_tallies, upload) are
+ * whole-cohort tallies and are neither used nor touched, so runs of other contexts on the same cohort are unaffected.
+ * Calls accumulate like nps_score_cohort_def (chunks of a larger matrix, with the same set).
+ * Formats: NPS_FMT_GT2X (what NPS_FMT_GT_AUTO gives; cohort_row0 a multiple of 128; definitions in magnitude bands are
+ * scored) and NPS_FMT_DS32 (any beta the two-pass kernels take).  NPS_E_UNSUPPORTED, with the format named: NPS_FMT_GT2,
+ * NPS_FMT_GT2M, NPS_FMT_DS16; and, with the row named, a definition with a row that NPS_FMT_GT2X cohorts score in their IEEE
+ * pass (nps_scoredef_create: a non-finite beta, an infinite eaf, an extreme weight) -- that pass recounts with whole-cohort
+ * tallies.  NPS_E_INVAL: the set's n_samples differs from the context's or the cohort's, or the set is on another device.
+ * Every refusal comes before the context changes.
+ * Not covered: the streamed nps_push_* rows, the several-scores passes (nps_score_cohort_multi), the nimpress command line. */
+int nps_score_cohort_def_subset(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0,
+                                const nps_scoredef *def, const nps_sampleset *s);
+/* nimpress.nim:643-649 for the kept samples: scores_out[n_kept] = sum / (2 nloci) + offset, the kept samples in cohort
+ * order (every sample kept: the bits of nps_finish); *nloci_out as for nps_finish.  After subset runs the sums of the dropped
+ * samples are meaningless -- their missing genotypes received the kept samples' imputation values -- and plain nps_finish
+ * returns UNSPECIFIED values at the dropped samples' positions.  _device: a caller-allocated DEVICE buffer of n_kept
+ * doubles. */
+int nps_finish_subset(nps_ctx *ctx, const nps_sampleset *s, double offset, double *scores_out, uint64_t *nloci_out);
+int nps_finish_subset_device(nps_ctx *ctx, const nps_sampleset *s, double offset, double *d_scores_out, uint64_t *nloci_out);
+
 /* ---- several score definitions in ONE pass over a resident cohort --------------------------
  * The reference evaluates one score per run (nimpress.nim:634-641); S scores over the same cohort are S
  * passes over the genotypes.  Here the S definitions are applied together, on either kind of cohort:

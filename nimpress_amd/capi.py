@@ -67,6 +67,8 @@ SYMBOLS = [
     "nps_multi_n_scores", "nps_multi_n_samples", "nps_multi_device", "nps_cohort_expect_passes", "nps_cohort_rows_tallied",
     "nps_live_resources", "nps_multi_row_tallies", "nps_multi_geometry",
     "nps_push_pl", "nps_cohort_push_pl", "nps_pl_likelihoods",
+    "nps_sampleset_create", "nps_sampleset_n_samples", "nps_sampleset_n_kept", "nps_sampleset_destroy",
+    "nps_score_cohort_def_subset", "nps_finish_subset", "nps_finish_subset_device",
 ]
 
 
@@ -215,6 +217,16 @@ def load(with_torch: bool = True):
     L.nps_push_pl.argtypes = [vp, vp, i32, i32, i32, i32, dbl, dbl]
     L.nps_cohort_push_pl.argtypes = [vp, u64, vp, i32, i32, i32]
     L.nps_pl_likelihoods.argtypes = [vp]
+    L.nps_sampleset_create.argtypes = [C.POINTER(vp), i32, u64, vp]
+    L.nps_sampleset_n_samples.argtypes = [vp]
+    L.nps_sampleset_n_samples.restype = u64
+    L.nps_sampleset_n_kept.argtypes = [vp]
+    L.nps_sampleset_n_kept.restype = u64
+    L.nps_sampleset_destroy.argtypes = [vp]
+    L.nps_sampleset_destroy.restype = None
+    L.nps_score_cohort_def_subset.argtypes = [vp, vp, u64, vp, vp]
+    L.nps_finish_subset.argtypes = [vp, vp, dbl, vp, C.POINTER(u64)]
+    L.nps_finish_subset_device.argtypes = [vp, vp, dbl, vp, C.POINTER(u64)]
     L.nps_live_resources.argtypes = []
     L.nps_live_resources.restype = C.c_int64
     _lib = L
@@ -402,6 +414,33 @@ class ScoreDef:
             pass
 
 
+class SampleSet:
+    """A chosen subset of a cohort's samples (nps_sampleset): keep[i] != 0 keeps sample i.  Scorer.score_cohort_def_subset
+    scores the kept samples as if they were the whole cohort; Scorer.finish_subset returns their scores in cohort order."""
+
+    def __init__(self, keep, device: int = 0):
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        assert keep.ndim == 1
+        self._h = C.c_void_p()
+        self.n_samples, self.device = int(keep.size), device
+        _check(load().nps_sampleset_create(C.byref(self._h), device, keep.size, keep.ctypes.data if keep.size else None))
+
+    @property
+    def n_kept(self) -> int:
+        return int(load().nps_sampleset_n_kept(self._h))
+
+    def close(self):
+        if self._h:
+            load().nps_sampleset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Scorer:
     """computePolygenicScores (nimpress.nim:592-649) with the row loop on the GPU."""
 
@@ -471,6 +510,24 @@ class Scorer:
     def score_cohort_def(self, cohort: Cohort, sdef: ScoreDef, cohort_row0: int = 0,
                          mode: int = MODE_AUTO):
         _check(load().nps_score_cohort_def(self._h, cohort._h, cohort_row0, sdef._h, mode))
+
+    def score_cohort_def_subset(self, cohort: Cohort, sdef: ScoreDef, sset: SampleSet, cohort_row0: int = 0):
+        """score the kept samples of `sset` as if they were the whole cohort (nps_score_cohort_def_subset: FMT_GT2X and
+        FMT_DS32 cohorts); calls accumulate like score_cohort_def"""
+        _check(load().nps_score_cohort_def_subset(self._h, cohort._h, cohort_row0, sdef._h, sset._h))
+
+    def finish_subset(self, sset: SampleSet, offset: float) -> Tuple[np.ndarray, int]:
+        """(scores of the kept samples in cohort order, nloci) -- nps_finish_subset"""
+        scores = np.empty(max(sset.n_kept, 1), dtype=np.float64)
+        nloci = C.c_uint64(0)
+        _check(load().nps_finish_subset(self._h, sset._h, float(offset), scores.ctypes.data, C.byref(nloci)))
+        return scores[: sset.n_kept], int(nloci.value)
+
+    def finish_subset_device(self, sset: SampleSet, offset: float, d_scores_ptr: int) -> int:
+        """kept samples' scores -> caller-allocated device buffer (n_kept float64); returns nloci."""
+        nloci = C.c_uint64(0)
+        _check(load().nps_finish_subset_device(self._h, sset._h, float(offset), C.c_void_p(d_scores_ptr), C.byref(nloci)))
+        return int(nloci.value)
 
     def finish_device(self, offset: float, d_scores_ptr: int) -> int:
         """scores -> caller-allocated device buffer (n_samples float64); returns nloci."""

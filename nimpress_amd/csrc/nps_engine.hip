@@ -21,6 +21,7 @@
 
 #include "nps_kernels.h"
 #include "nps_own.h"
+#include "nps_subset_mask.h"
 
 using namespace nps;
 
@@ -143,6 +144,21 @@ static int cohort_quiesce(const nps_cohort *c) {
     return NPS_OK;
 }
 
+// A chosen subset of a cohort's samples (nps_score_cohort_def_subset): the mask of nps_subset_mask.h on the device,
+// immutable after creation -- contexts on several threads may share one.
+struct nps_sampleset {
+    int device = 0;
+    uint64_t n_samples = 0, n_kept = 0;
+    DevBuf<uint32_t> d_bits;             // one bit per sample (the masked dosage tally, the gather)
+    DevBuf<unsigned long long> d_unit;   // one word per unit of the strip layout (the masked strip tally)
+    DevBuf<uint32_t> d_prefix;           // kept samples in front of every word of d_bits (the gather)
+
+    ~nps_sampleset() {  // queued work may still read the mask
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
+};
+
 struct PendingRow {
     int32_t batch_idx;  // >= 0: index into the open GT / DS batch's device stats; -1: host stat
     int32_t is_ds;      // which open batch batch_idx refers to
@@ -203,6 +219,7 @@ struct nps_ctx {
     // writer overwrites), 1 = chunk 0 only (fused epilogues), n_chunks = all (two-pass kernels)
     uint32_t chunks_used = 0;
     DevBuf<double> d_scores;
+    DevBuf<double> d_subset_scores;          // nps_finish_subset: the kept samples' scores on their way to the host
     DevBuf<unsigned long long> d_nloci;      // [0] used rows counted on the device, [1] sticky status bits
     unsigned long long *h_result = nullptr;  // pinned copy of that block
     bool broken = false;                     // a launch sequence failed half-way: nps_reset first
@@ -902,6 +919,61 @@ extern "C" int nps_finish_device(nps_ctx *c, double offset, double *d_scores_out
     if (c->n && !d_scores_out) return fail(NPS_E_INVAL, "d_scores_out is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return finish_common(c, offset, d_scores_out, nullptr, nloci_out);
+}
+
+// nps_finish for the kept samples of a set: finish_kernel makes every sample's score as nps_finish does (the same
+// arithmetic, so a set that keeps everybody returns nps_finish's bits), the gather takes the kept ones, in cohort
+// order, into d_dst[n_kept]
+static int check_sampleset(const nps_ctx *c, const nps_sampleset *s) {
+    if (!s) return fail(NPS_E_INVAL, "sample set is NULL");
+    if (s->device != c->device) return fail(NPS_E_INVAL, "sample set and context are on different devices");
+    if (s->n_samples != c->n)
+        return fail(NPS_E_INVAL, "sample set has %llu samples, context %llu", (unsigned long long)s->n_samples,
+                    (unsigned long long)c->n);
+    return NPS_OK;
+}
+
+static int finish_subset_common(nps_ctx *c, const nps_sampleset *s, double offset, double *d_dst, double *h_scores_out,
+                                uint64_t *nloci_out) {
+    int rc = run_batch(c);
+    if (rc) return rc;
+    {
+        ProfScope ps(c, P_REDUCE);
+        HIP_TRY(launch_finish(c->stream.get(), c->d_part.get(), c->chunks_used, c->geom.part_chunk_stride, c->n, c->const_sum,
+                              c->d_nloci.get(), c->host_nloci, 1, offset, c->d_scores.get()));
+        HIP_TRY(launch_subset_gather(c->stream.get(), c->d_scores.get(), c->n, s->d_bits.get(), s->d_prefix.get(), d_dst));
+    }
+    rc = fetch_result(c);
+    if (rc) return rc;
+    if (h_scores_out)
+        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * s->n_kept, hipMemcpyDeviceToHost, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    rc = check_status(c);
+    if (rc) return rc;
+    if (nloci_out) *nloci_out = c->host_nloci + c->h_result[0];
+    return NPS_OK;
+}
+
+extern "C" int nps_finish_subset(nps_ctx *c, const nps_sampleset *s, double offset, double *scores_out, uint64_t *nloci_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    rc = check_sampleset(c, s);
+    if (rc) return rc;
+    if (!scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->d_subset_scores.ensure(s->n_kept, c->stream.get()));
+    return finish_subset_common(c, s, offset, c->d_subset_scores.get(), scores_out, nloci_out);
+}
+
+extern "C" int nps_finish_subset_device(nps_ctx *c, const nps_sampleset *s, double offset, double *d_scores_out,
+                                        uint64_t *nloci_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    rc = check_sampleset(c, s);
+    if (rc) return rc;
+    if (!d_scores_out) return fail(NPS_E_INVAL, "d_scores_out is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return finish_subset_common(c, s, offset, d_scores_out, nullptr, nloci_out);
 }
 
 extern "C" int nps_partial_device(nps_ctx *c, double *d_sums_out, uint64_t *nloci_out) {
@@ -1709,8 +1781,9 @@ static int mx_run_buffers(nps_ctx *c, const nps_cohort *co, const nps_scoredef *
 }
 
 // NPS_FMT_GT2X: one pass per magnitude band of the definition (normally one) on the route mx_route chose
+// (set: a subset run -- route GivenTallied, its tally pass counted under the set's mask, the decisions with N = kept samples)
 static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
-                        const MxRouted &mx) {
+                        const MxRouted &mx, const nps_sampleset *set) {
     const MxPlan &mxp = mx.plan;
     const MxRoute route = mx.route;
     const size_t n_bands = std::max<size_t>(1, def->mx_bands.size());  // (no bands: the definition is its one band)
@@ -1720,9 +1793,10 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
     r.n_sb_cohort = gt2x_superblocks(co->n_rows);
     r.sb0 = cohort_row0 >> 7;
     r.n_samples = c->n;
+    r.n_decide = set ? set->n_kept : c->n;
     r.n_rows = def->m;
     r.prm = dev_params(c->params);
-    r.t_maxmis = maxmis_threshold(c->n, c->params.max_missing_rate);
+    r.t_maxmis = maxmis_threshold(r.n_decide, c->params.max_missing_rate);
     r.d_tally = c->d_rtally.get();
     r.d_const_sum = c->d_mx_const.get() + 8;
     r.d_cpart = c->d_mx_cpart.get();
@@ -1756,7 +1830,11 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         if (rc) return rc;
         if (route == MxRoute::GivenTallied) {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_mx_tally(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally.get()));
+            if (set)
+                HIP_TRY(launch_mx_tally_masked(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, set->d_unit.get(),
+                                               c->d_rtally.get()));
+            else
+                HIP_TRY(launch_mx_tally(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally.get()));
         }
         hipError_t fe;
         {
@@ -1796,13 +1874,16 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
 }
 
 // NPS_FMT_DS32 / NPS_FMT_DS16: the single-read kernel (plan.ok), else -- float32 rows only -- tally, params, accumulate
+// (set: a subset run -- always the three launches, the tally counted under the set's mask and the decisions with N = kept
+// samples; the accumulation is the cohort's)
 static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
-                        int mode, const FusedPlan &plan, uint64_t n_tally) {
+                        int mode, const FusedPlan &plan, uint64_t n_tally, const nps_sampleset *set) {
     const uint64_t m = def->m;
+    const uint64_t n_decide = set ? set->n_kept : c->n;
     const bool is_ds16 = co->format == NPS_FMT_DS16;
     const uint64_t stride_f = co->stride_bytes / 4;  // (NPS_FMT_DS32 only below the fused branch)
     const float *ds = (const float *)((const char *)co->d_data.get() + cohort_row0 * co->stride_bytes);
-    if (plan.ok && c->n) {
+    if (plan.ok && c->n && !set) {
         bool ran = false;
         int rc = single_read(c, guard, plan, n_tally, "fused DS", mode == NPS_MODE_AUTO && !is_ds16, [&]() {
             return launch_ds_fused(c->stream.get(), plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc.get(),
@@ -1824,12 +1905,16 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         const uint64_t k = std::min(block_rows, m - r0);
         {
             ProfScope ps(c, P_TALLY);
-            HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0,
-                                    k, c->d_rds_tally.get() + r0));
+            if (set)
+                HIP_TRY(launch_ds_tally_masked(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0, k,
+                                               set->d_bits.get(), c->d_rds_tally.get() + r0));
+            else
+                HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0,
+                                        k, c->d_rds_tally.get() + r0));
         }
         {
             ProfScope ps(c, P_PARAMS);
-            HIP_TRY(launch_ds_params(c->stream.get(), c->d_rds_tally.get() + r0, def->d_desc.get() + r0, k, c->n,
+            HIP_TRY(launch_ds_params(c->stream.get(), c->d_rds_tally.get() + r0, def->d_desc.get() + r0, k, n_decide,
                                      dev_params(c->params), c->d_rds_rowp.get() + r0, c->d_rstats.get() + r0,
                                      c->d_nloci.get()));
         }
@@ -1943,8 +2028,9 @@ static int fused_plan_for_run(nps_ctx *c, const nps_cohort *co, uint64_t m, int 
 // mode).  The rows without genotype data are applied, and the run is registered for nps_flush, only
 // once all launches have been queued; a failure between the first and the last launch marks the
 // context broken (NPS_E_STATE until nps_reset).
-extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0,
-                                    const nps_scoredef *def, int mode) {
+// set: nps_score_cohort_def_subset (mode NPS_MODE_TWOPASS: the routes that count the tallies in a pass of their own), else null
+static int score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def, int mode,
+                            const nps_sampleset *set) {
     int rc = check_usable(c);
     if (rc) return rc;
     if (!co || !def) return fail(NPS_E_INVAL, "cohort or scoredef is NULL");
@@ -2056,15 +2142,88 @@ extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t c
     // ---- launches
     RunGuard guard{c};
     if (is_mx)
-        rc = c->n ? score_run_mx(c, guard, co, cohort_row0, def, mx) : NPS_OK;
+        rc = c->n ? score_run_mx(c, guard, co, cohort_row0, def, mx, set) : NPS_OK;
     else if (is_ds)
-        rc = score_run_ds(c, guard, co, cohort_row0, def, mode, plan, n_tally);
+        rc = score_run_ds(c, guard, co, cohort_row0, def, mode, plan, n_tally, set);
     else
         rc = score_run_gt2(c, guard, co, cohort_row0, def, mode, plan, n_tally);
     if (rc) return rc;
     commit();
     guard.ok = true;
     return NPS_OK;
+}
+
+extern "C" int nps_score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0,
+                                    const nps_scoredef *def, int mode) {
+    return score_cohort_def(c, co, cohort_row0, def, mode, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// a subset of a resident cohort's samples (the kernels: nps_subset.hip)
+extern "C" int nps_sampleset_create(nps_sampleset **out, int device, uint64_t n_samples, const uint8_t *keep) {
+    if (!out) return fail(NPS_E_INVAL, "out is NULL");
+    *out = nullptr;
+    if (!keep) return fail(NPS_E_INVAL, "keep is NULL");
+    if (n_samples == 0) return fail(NPS_E_INVAL, "a sample set of no samples");
+    if (n_samples > 0x7fffffffull) return fail(NPS_E_UNSUPPORTED, "n_samples %llu exceeds 2^31-1", (unsigned long long)n_samples);
+    const SubsetMask m = subset_mask(keep, n_samples);
+    if (m.n_kept == 0) return fail(NPS_E_INVAL, "the sample set keeps none of its %llu samples", (unsigned long long)n_samples);
+    int rc = select_device(device);
+    if (rc) return rc;
+    std::unique_ptr<nps_sampleset> owner(new (std::nothrow) nps_sampleset);
+    nps_sampleset *s = owner.get();
+    if (!s) return fail(NPS_E_NOMEM, "out of host memory");
+    s->device = device;
+    s->n_samples = n_samples;
+    s->n_kept = m.n_kept;
+    HIP_TRY(s->d_bits.alloc(m.bits.size()));
+    HIP_TRY(s->d_unit.alloc(m.unit.size()));
+    HIP_TRY(s->d_prefix.alloc(m.prefix.size()));
+    HIP_TRY(hipMemcpy(s->d_bits.get(), m.bits.data(), sizeof(uint32_t) * m.bits.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_unit.get(), m.unit.data(), sizeof(uint64_t) * m.unit.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_prefix.get(), m.prefix.data(), sizeof(uint32_t) * m.prefix.size(), hipMemcpyHostToDevice));
+    *out = owner.release();
+    return NPS_OK;
+}
+extern "C" uint64_t nps_sampleset_n_samples(const nps_sampleset *s) { return s ? s->n_samples : 0; }
+extern "C" uint64_t nps_sampleset_n_kept(const nps_sampleset *s) { return s ? s->n_kept : 0; }
+extern "C" void nps_sampleset_destroy(nps_sampleset *s) { delete s; }
+
+static const char *format_name(int format) {
+    switch (format) {
+    case NPS_FMT_GT2: return "NPS_FMT_GT2";
+    case NPS_FMT_DS32: return "NPS_FMT_DS32";
+    case NPS_FMT_GT2M: return "NPS_FMT_GT2M";
+    case NPS_FMT_GT2X: return "NPS_FMT_GT2X";
+    case NPS_FMT_DS16: return "NPS_FMT_DS16";
+    default: return "unknown format";
+    }
+}
+
+// Everything is refused before the context changes, as for nps_score_cohort_def.  The run takes the routes that count the
+// rows' tallies in a pass of their own (NPS_MODE_TWOPASS) into the CONTEXT's tally buffer: the tallies a cohort keeps are
+// whole-cohort tallies and are neither read nor written here.
+extern "C" int nps_score_cohort_def_subset(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                                           const nps_sampleset *s) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    if (!co || !def) return fail(NPS_E_INVAL, "cohort or scoredef is NULL");
+    rc = check_sampleset(c, s);
+    if (rc) return rc;
+    if (s->n_samples != co->n_samples)
+        return fail(NPS_E_INVAL, "sample set has %llu samples, cohort %llu", (unsigned long long)s->n_samples,
+                    (unsigned long long)co->n_samples);
+    if (co->format != NPS_FMT_GT2X && co->format != NPS_FMT_DS32)
+        return fail(NPS_E_UNSUPPORTED, "a subset of the samples is scored on NPS_FMT_GT2X and NPS_FMT_DS32 cohorts; this one is %s",
+                    format_name(co->format));
+    if (co->format == NPS_FMT_GT2X && !def->special.empty()) {
+        // (the IEEE pass of such rows, mx_special_pass, recounts them with whole-cohort tallies)
+        uint64_t j = 0;
+        while (j < def->n_desc && def->data_index[j] != (int64_t)def->special[0]) ++j;
+        return fail(NPS_E_UNSUPPORTED, "row %llu has a non-finite or extreme beta or an infinite eaf: NPS_FMT_GT2X cohorts score "
+                    "such rows in an IEEE pass of whole-cohort tallies, which a subset run cannot use", (unsigned long long)j);
+    }
+    return score_cohort_def(c, co, cohort_row0, def, NPS_MODE_TWOPASS, s);
 }
 
 extern "C" int nps_score_cohort(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0,

@@ -325,9 +325,12 @@ hipError_t mx_plan(int device, uint64_t n_samples, uint64_t n_rows, bool two_pas
 struct MxRun {
     const void *d_units = nullptr;  // the cohort, of n_sb_cohort superblocks; the run starts at superblock sb0
     uint64_t n_sb_cohort = 0, sb0 = 0, n_samples = 0, n_rows = 0;
+    // the N of the rows' decisions (nmissing / N > --maxmis, ngenotyped = N - nmissing): the cohort's samples, or the kept
+    // ones of a subset run (nps_subset.hip), whose tallies count them alone; n_samples stays the fold's sample count
+    uint64_t n_decide = 0;
     const nps_row_desc *d_desc = nullptr;
     DevParams prm{};
-    int64_t t_maxmis = -1;  // largest nmissing with !((double)nmissing / (double)N > --maxmis)
+    int64_t t_maxmis = -1;  // largest nmissing with !((double)nmissing / (double)N > --maxmis), N = n_decide
     int F = 0;              // fixed-point scale 2^F with |beta| (4 + max(2, 2 |eaf|)) 2^F < 2^56 for every row
     unsigned long long *d_tally = nullptr;  // [plan.n_sb * 128], zero on entry and again after launch_mx_fold
     nps_locus_stat *d_stats = nullptr;
@@ -378,5 +381,17 @@ hipError_t launch_gt2x_to_rows(hipStream_t st, const void *d_units, uint64_t n_s
 // a whole NPS_FMT_GT2 cohort (plain order) -> units and tally words (d_tally: [n_sb * 128], zero on entry)
 hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
                                      uint64_t n_rows, void *d_units, unsigned long long *d_tally);
+
+// ---- a subset of a resident cohort's samples (nps_subset.hip; the mask: nps_subset_mask.h) -----------------------------
+// launch_mx_tally under a mask: d_unit_mask holds one 64-bit word per unit of the cohort (sample s of the unit in bits
+// 2s, 2s + 1); the same tally words, counted over the kept samples
+hipError_t launch_mx_tally_masked(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
+                                  const unsigned long long *d_unit_mask, unsigned long long *d_tally);
+// launch_ds_tally under a mask: d_bits holds one bit per sample, ceil(n / 32) words
+hipError_t launch_ds_tally_masked(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n, const nps_row_desc *d_desc,
+                                  uint64_t n_rows, const uint32_t *d_bits, DsTally *d_tally);
+// d_out[position of i among the kept samples] = d_scores[i] for every kept sample i < n
+hipError_t launch_subset_gather(hipStream_t st, const double *d_scores, uint64_t n, const uint32_t *d_bits,
+                                const uint32_t *d_prefix, double *d_out);
 
 }  // namespace nps

@@ -983,7 +983,7 @@ hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const MxRun &r) {
     a.sb0 = (uint32_t)r.sb0;
     a.n_sb = plan.n_sb;
     a.n_rows = r.n_rows;
-    a.n_samples = r.n_samples;
+    a.n_samples = r.n_decide;  // (what the rows' decisions divide by: mx_row)
     a.P = plan.grid_P;
     a.nu_last = plan.grid_nu_last;
     a.U = plan.grid_U;

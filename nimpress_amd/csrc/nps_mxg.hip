@@ -324,7 +324,7 @@ hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const MxRun &r) {
     MxArgs ra{};  // (what mx_row reads; everything else null / zero)
     ra.n_sb = plan.n_sb;
     ra.n_rows = r.n_rows;
-    ra.n_samples = r.n_samples;
+    ra.n_samples = r.n_decide;  // (what the rows' decisions divide by: mx_row)
     ra.P = plan.P;
     ra.nu_last = plan.nu_last;
     ra.Q = plan.Q;
