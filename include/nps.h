@@ -383,8 +383,8 @@ int nps_score_cohort(nps_ctx *ctx, const nps_cohort *c, uint64_t cohort_row0,
  * +-inf gives NaN where the dosage is 0 (0 x inf) and +-inf elsewhere, NaN propagates, a NaN imputed dosage times a zero
  * beta stays NaN, nloci = 0 gives NaN, and sums that overflow are +-inf -- on every format and mode, NaN, +inf and -inf
  * at the same samples as the reference's.  Rows the NPS_FMT_GT2X fixed-point kernels cannot carry (a non-finite beta,
- * an infinite eaf, |beta| (4 + max(2, 2 |eaf|)) outside [2^-900, 2^1000)) are scored there in an IEEE double pass of
- * their own after the fixed-point pass. */
+ * an infinite eaf, a non-zero beta with |beta| (4 + max(2, 2 |eaf|)) outside [2^-900, 2^1000), a NaN eaf counting as 0
+ * there) are scored there in an IEEE double pass of their own after the fixed-point pass. */
 int nps_scoredef_create(nps_scoredef **out, int device, const nps_row_desc *rows, uint64_t n_desc);
 uint64_t nps_scoredef_n_present(const nps_scoredef *d); /* rows that consume a cohort row */
 void nps_scoredef_destroy(nps_scoredef *d);
@@ -463,7 +463,11 @@ int nps_finish_subset_device(nps_ctx *ctx, const nps_sampleset *s, double offset
  * one); scores of a dosage cohort carry the bound of the single-score DS paths -- plain float64: every term d x beta
  * rounded once, the running sum once per row -- and any finite dosage is taken, not only [0, 2].  A definition's column
  * of a dosage pass has the same bits whatever other definitions share the pass.  beta must be finite and eaf not
- * infinite (NPS_E_UNSUPPORTED otherwise, naming the row; a NaN eaf is scored).
+ * infinite (NPS_E_UNSUPPORTED otherwise, naming the row; a NaN eaf is scored).  A definition of finite betas whose weight
+ * bound max|beta| (3 + max(2, 2 max|eaf|)) over its listed rows (NaN eafs aside) is not finite -- |beta| = DBL_MAX -- has no
+ * fixed-point scale: nps_multidef_create takes it, a dosage cohort scores it in float64 as the reference does, and
+ * nps_score_cohort_multi on a NPS_FMT_GT2M cohort refuses it with NPS_E_UNSUPPORTED, naming the score, before the context
+ * changes.
  *
  * ref_is_effect on a dosage cohort: 1 = the effect allele is REF, the dosage is 2 - DS (and the homref imputation
  * value 2); with NPS_RIE_COUNTS_EFFECT set the row ALREADY counts the effect allele -- no 2 - DS -- and bit 0 alone

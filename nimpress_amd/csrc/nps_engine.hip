@@ -2370,6 +2370,7 @@ struct nps_multidef {
     DevBuf<nps_row_desc> d_desc;     // [S][n_desc]
     DevBuf<int> d_F;                 // fixed-point exponent per score: weight * 2^F is an integer below 2^(8 ND - 9)
     int ND = 7;                      // base-256 digits per weight
+    int no_scale = -1;               // first score whose weight bound is not finite: no fixed-point scale (NPS_FMT_GT2M refuses it)
 
     ~nps_multidef() {  // a pass that reads the definitions may still be queued
         (void)hipSetDevice(device);
@@ -2389,6 +2390,7 @@ extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const np
     if (n_desc && !rows) return fail(NPS_E_INVAL, "rows is NULL");
     if (n_desc > 0xfffffff0ull) return fail(NPS_E_UNSUPPORTED, "too many rows");
     int F[NPS_MULTI_MAX_SCORES];
+    int no_scale = -1;
     for (int s = 0; s < n_scores; ++s) {
         double maxb = 0.0, maxe = 0.0, minb = HUGE_VAL;
         for (uint64_t j = 0; j < n_desc; ++j) {
@@ -2419,8 +2421,15 @@ extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const np
                         s, maxb / minb, minb, maxb, ND == 7 ? 25 : 17, 8 * ND - 7);
         // largest weight a row can have: |beta| * max(|imputed - 3|, |locus constant|)
         const double bound = maxb * (3.0 + std::max(2.0, 2.0 * maxe));
+        // Finite betas whose bound overflows (|beta| = DBL_MAX) have no scale: frexp leaves e unspecified, and the weights
+        // beta x 2^F would not be integers llrint can hold.  The dosage formats score such a definition in plain float64,
+        // so it is not refused here but by nps_score_cohort_multi on a NPS_FMT_GT2M cohort.
         int e = 0;
-        if (bound > 0.0) (void)std::frexp(bound, &e);  // bound < 2^e
+        if (!std::isfinite(bound)) {
+            if (no_scale < 0) no_scale = s;
+        } else if (bound > 0.0) {
+            (void)std::frexp(bound, &e);  // bound < 2^e
+        }
         F[s] = 8 * ND - 9 - e;  // the kernel's coefficients (up to 160 x weight) stay below 2^(8 ND - 1)
     }
     int rc = select_device(device);
@@ -2431,6 +2440,7 @@ extern "C" int nps_multidef_create_bits(nps_multidef **out, int device, const np
     d->device = device;
     d->S = n_scores;
     d->ND = ND;
+    d->no_scale = no_scale;
     d->n_desc = n_desc;
     HIP_TRY(d->d_F.alloc(NPS_MULTI_MAX_SCORES));
     HIP_TRY(hipMemcpy(d->d_F.get(), F, sizeof(int) * n_scores, hipMemcpyHostToDevice));
@@ -2615,6 +2625,10 @@ extern "C" int nps_score_cohort_multi(nps_multi *m, const nps_cohort *co, uint64
     int rc = check_range(co, cohort_row0, def->n_desc);
     if (rc) return rc;
     if (def->n_desc == 0) return NPS_OK;
+    if (!is_ds && def->no_scale >= 0)
+        return fail(NPS_E_UNSUPPORTED, "score %d: the weight bound max|beta| (3 + max(2, 2 max|eaf|)) is not finite, beyond "
+                    "the fixed-point weights of a NPS_FMT_GT2M pass; score this definition on a dosage cohort or with the "
+                    "single-score path (nps_scoredef_create / nps_score_cohort_def)", def->no_scale);
     HIP_TRY(hipSetDevice(m->device));
     if (is_ds) {
         rc = cohort_quiesce(co);  // rows pushed into the cohort (nps_cohort_push_pl) are complete

@@ -210,6 +210,9 @@ class Decide:
     def over(self, k, n, r):          # nimpress.nim:565
         return float(k) / float(n) > r
 
+    def tally(self, j, k, neffect, n):   # row j's (nmissing, neffect) as counted; a subset run counts the kept samples
+        return k, neffect
+
     def ngen(self, k, n):
         return n - k
 
@@ -246,7 +249,32 @@ FAULTS = {
     "mincs_vs_n": _fault(enough=lambda s, k, n, mincs: float(n) >= float(mincs)),
     "ngen_padded": _fault(ngen=lambda s, k, n: _pad(n, 16) - k),
 }
-MAXMIS_FAULTS = [f for f in FAULTS if not (f.startswith("mincs") or f == "ngen_padded")]
+
+
+def _n_total(n):
+    import wide_cases
+    return wide_cases.n_total(n)
+
+
+def _leak(s, j, k, neffect, n):
+    """the tallies of row j taken over the wide matrix of wide_cases.widen: its dropped columns are missing in the even
+    rows and hold dosage 2 in the odd ones"""
+    extra = _n_total(n) - n
+    return (k + extra, neffect) if j % 2 == 0 else (k, neffect + 2.0 * extra)
+
+
+# What a subset run (nps_score_cohort_def_subset) can get wrong: the sample count of the decisions is n_kept = n, that of
+# the layout is n_total (tests/wide_cases.py) -- a mix-up of the two in the --maxmis quotient, in ngenotyped or in the
+# --mincs test, and tallies that count dropped samples.
+SUBSET_FAULTS = {
+    "over_whole": _fault(over=lambda s, k, n, r: float(k) / float(_n_total(n)) > r),
+    "ngen_whole": _fault(ngen=lambda s, k, n: _n_total(n) - k),
+    "enough_whole": _fault(enough=lambda s, k, n, mincs: float(_n_total(n) - k) >= float(mincs)),
+    "leak": _fault(tally=_leak),
+}
+FAULTS.update(SUBSET_FAULTS)
+MINCS_FAULTS = ["mincs_gt", "mincs_vs_n", "ngen_padded", "ngen_whole", "enough_whole"]
+MAXMIS_FAULTS = [f for f in FAULTS if f not in MINCS_FAULTS]
 
 REASON_GENOTYPED, REASON_MAXMIS = 0, 4   # include/nps.h, oracle/refcpu.py REASON_NAMES
 
@@ -279,8 +307,8 @@ def reference(codes, d, decide=None):
         rie, beta, eaf = bool(d["rie"][j]), d["beta"][j], d["eaf"][j]
         dos = spc.dosages(codes[j])
         miss = np.isnan(dos)
-        k = int(miss.sum())
-        ngen, neffect = decide.ngen(k, n), float(np.sum(dos[~miss]))
+        k, neffect = decide.tally(j, int(miss.sum()), float(np.sum(dos[~miss])), n)
+        ngen = decide.ngen(k, n)
         used, reason = 1, REASON_GENOTYPED
         if decide.over(k, n, p["maxmis"]):             # :565-571
             reason = REASON_MAXMIS

@@ -9,6 +9,9 @@
   for the --mincs decision (a row is used and "genotyped" either way), so for mincs_gt, mincs_vs_n and ngen_padded the
   moved decision is the one the scorer takes (Decide.enough), and the rejection rests on the scores and ngenotyped.
 * The rows have exactly the missing counts asked for, where asked for, and every t equals the scan's result.
+* The faults of a subset run (decision_cases.SUBSET_FAULTS: the layout's sample count where n_kept belongs, tallies that
+  count dropped samples) are rejected at 777 and at 4 000 samples each, and the wide embedding the subset paths score
+  (tests/wide_cases.py) has the units its layout promises.
 """
 import numpy as np
 import pytest
@@ -16,6 +19,7 @@ import pytest
 import decision_cases as dc
 import exact_reference as er
 import special_cases as spc
+import wide_cases as wc
 from oracle import refcpu
 
 SMALL_CASES = [(n, name) for n in dc.SMALL_N for name in dc.table(n).specs()]
@@ -74,9 +78,9 @@ def moved(n, name, fault):
     row under int_fail, 0 / 0 or the fall-back)"""
     T, F = dc.table(n), dc.FAULTS[fault]
     p, rows = T.specs()[name][0], T.specs()[name][3]
-    for k in T.counts[:rows]:
+    for j, k in enumerate(T.counts[:rows]):
         o = dc.EXACT.over(k, n, p["maxmis"])
-        if F.over(k, n, p["maxmis"]) != o:
+        if F.over(F.tally(j, k, 0.0, n)[0], n, p["maxmis"]) != o:
             return True
         if not o and p["imp_sample"] in ("int_ps", "int_fail") and k > 0 and (k < n or p["imp_sample"] == "int_ps") and \
                 F.enough(k, n, p["mincs"]) != dc.EXACT.enough(k, n, p["mincs"]):
@@ -119,6 +123,53 @@ def test_every_fault_is_rejected_on_the_small_shapes(fault):
             assert not name.endswith("int_ps") or rejected(bad, ref, d["beta"], False, what), what
         seen += rejected(bad, ref, d["beta"], False, what)
     assert seen and any(name.startswith("mincs_triple") or fault in dc.MAXMIS_FAULTS for _, name in killers)
+
+
+@pytest.mark.parametrize("n", dc.SMALL_N)
+@pytest.mark.parametrize("fault", list(dc.SUBSET_FAULTS))
+def test_subset_faults_are_rejected_at_each_small_shape(fault, n):
+    """the mistakes of a subset run (the layout's n_total where n_kept belongs, tallies that count dropped samples): at
+    each of the two small sample counts on its own, some case is rejected by the comparison -- with the statistics, as
+    the subset paths return them"""
+    T = dc.table(n)
+    assert wc.n_total(n) > n
+    for name in T.specs():
+        if not moved(n, name, fault):
+            continue
+        d = T.definition(name)
+        ref = dc.reference(T.codes(), d)
+        bad = dc.reference(T.codes(), d, dc.FAULTS[fault])
+        if rejected(bad, ref, d["beta"], True, "%s, %s at %d" % (fault, name, n)):
+            return
+    raise AssertionError("no case at %d samples rejects %s" % (n, fault))
+
+
+@pytest.mark.parametrize("n", [33, 777, 1500, 3000, 4000, 70000])
+def test_wide_layout_is_what_the_subset_paths_need(n):
+    rng = np.random.default_rng(n)
+    codes = rng.integers(0, 4, size=(5, n), dtype=np.uint8)
+    wide, keep = wc.widen(codes)
+    assert keep.dtype == np.uint8 and wide.shape == (5, keep.size) and keep.size == wc.n_total(n)
+    assert np.array_equal(wide[:, keep != 0], codes)                       # the kept columns, in order
+    assert (wide[0::2][:, keep == 0] == 2).all() and (wide[1::2][:, keep == 0] == 3).all()
+    kept, size = wc.unit_masks(keep)
+    assert keep.size % wc.UNIT != 0 and size[-1] < wc.UNIT and not keep[-wc.TAIL:].any()   # ragged last unit, dropped tail
+    assert np.count_nonzero(kept[:-1] == 0) >= 2                            # wholly dropped units
+    assert np.count_nonzero((kept > 0) & (kept < size)) >= 1                # mixed masks
+    if n >= 128:                                                            # wholly kept units
+        assert np.count_nonzero(kept[:-1] == wc.UNIT) >= 1
+    if n >= 2048:
+        assert wc.longest_dropped_run(keep) >= 2048
+    if n == 4000:    # the eight-fold unrolled loop of the masked dosage tally and its tail loop both run
+        assert keep.size > 7168
+    if n == 70000:   # four groups of sixteen strips in the masked strip tally
+        assert (keep.size + wc.STRIP - 1) // wc.STRIP == 53
+    # a leak shows: the tallies over the wide matrix differ from the kept ones in every row
+    nm, ne = dc.tallies(codes)
+    nmw, new = dc.tallies(wide)
+    assert ((nmw != nm) | (new != ne)).all() and np.abs((nmw - nm) + (new - ne)).min() >= keep.size - n
+    ds = wc.ds_rows(wide, np.array([0, 1, 0, 1, 0]))
+    assert ds.dtype == np.float32 and np.array_equal(np.isnan(ds).sum(axis=1), nmw)
 
 
 # which threshold of which shape tells which fault from the reference (a scan over the boundary counts, run once):

@@ -20,7 +20,7 @@ import special_cases as spc
 from conftest import need_free_hbm
 from nimpress_amd import capi
 from test_gpu_parity import PARAM_GRID, make_cohort, make_ds16_cohort, make_ds_cohort
-from test_gpu_special_values import PATHS, STRIP_PATHS, STRIP_SHAPES, Data
+from test_gpu_special_values import EARLIER_PATHS, PATHS, STRIP_PATHS, STRIP_SHAPES, Data, refused
 
 pytestmark = pytest.mark.gpu
 
@@ -90,14 +90,16 @@ def data():
 
 def check_exact(D, key, path):
     d, ref, nl = D.exact(key)
+    what = "%s pk %d on %s (%d x %d)" % (key[0], key[1], path, D.n, D.m)
+    assert not refused(path, d, lambda: PATHS[path](D, d), what), what + ": an exact design no path refuses"
     scores, nloci, _ = PATHS[path](D, d)
     assert nloci == nl
-    assert_same_bits(scores, ref, "%s pk %d on %s (%d x %d)" % (key[0], key[1], path, D.n, D.m))
+    assert_same_bits(scores, ref, what)
 
 
 @pytest.mark.parametrize("over", [True, False])
 @pytest.mark.parametrize("pk", range(len(PARAM_GRID)))
-@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("path", EARLIER_PATHS)
 def test_exact_design_small(data, path, pk, over):
     """rows over --maxmis (s_const on the strip paths) with `over`; without, every row's missing genotypes imputed"""
     check_exact(data(SMALL, over), ("plain", pk), path)
@@ -115,7 +117,12 @@ def test_exact_design_strip_plans(data, shape, path, pk):
 @pytest.mark.parametrize("pk", [0, 1, 6])
 @pytest.mark.parametrize("path", STRIP_PATHS + ["gt2x_row0_128", "partial_gt2x", "gt2_fused", "push_packed"])
 def test_exact_two_band_definition(data, path, pk):
-    D = data((1500, 60) if path in STRIP_PATHS else SMALL)
+    check_two_band(data, path, pk)
+
+
+def check_two_band(data, path, pk):
+    """(subset_gt2x: the strip arithmetic under the mask, one masked tally per band)"""
+    D = data((1500, 60) if path in STRIP_PATHS + ["subset_gt2x"] else SMALL)
     assert len(er.strip_bands(D.definition(("two_band", pk))["beta"], D.eaf)[1]) == 2
     check_exact(D, ("two_band", pk), path)
 
@@ -219,16 +226,22 @@ PROBE_PARAMS = dict(imp_locus="ps", imp_missing="homref", imp_sample="homref", m
 
 
 PROBE_RUNS = STRIP_RUNS + [((1500, 2000), "gt2x_row0_128"), ((1500, 2000), "partial_gt2x")]
+# (the subset run is the strip arithmetic; the design's power-of-two genotyped counts hold because N = n_kept = n)
+SUBSET_PROBE_RUNS = [((1500, 2000), "subset_gt2x")]
+PROBE_BANDS = (1, 3, 4, 5, 6, 7, 8)
 INT_PS_PROBE = dict(imp_locus="ps", imp_missing="homref", imp_sample="int_ps", maxmis=1.0, mincs=0)
 
 
-@pytest.mark.parametrize("shape,path,n_bands", [(s, p, b) for s, p in PROBE_RUNS for b in (1, 3, 4, 5, 6, 7, 8)])
+@pytest.mark.parametrize("shape,path,n_bands", [(s, p, b) for s, p in PROBE_RUNS for b in PROBE_BANDS])
 def test_digit_probes_strip(data, shape, path, n_bands):
+    check_digit_probes(data(shape), shape, path, n_bands)
+
+
+def check_digit_probes(D, shape, path, n_bands):
     """full-mantissa betas, one set per magnitude band (beta 2^F_b = 53-bit integers over fourteen digits): bit for bit
     what the kernels' arithmetic gives -- each band's exact integer sum rounded once, scaled, the bands added in order
     (nps_mx.hip:604-607); under homref a missing genotype weighs 0 or 2 w1, under int_ps rn(fl(imp w1)) with the
     design's power-of-two genotyped counts (nps_mx_common.h:166-170)"""
-    D = data(shape)
     beta, eaf = er.banded_probe_betas(D.m, n_bands, 3), np.full(D.m, 0.25)
     assert len(er.strip_bands(beta, eaf)[1]) == min(n_bands, D.m)
     for params in (PROBE_PARAMS, INT_PS_PROBE):
@@ -251,7 +264,7 @@ class RealData(Data):
         self.cohorts, self.ref = {}, {}
 
 
-GT2X_PATHS = STRIP_PATHS + ["gt2x_row0_128", "partial_gt2x"]
+GT2X_PATHS = STRIP_PATHS + ["gt2x_row0_128", "partial_gt2x", "subset_gt2x"]
 
 
 @pytest.fixture(scope="module")
@@ -262,13 +275,19 @@ def real():
 
 
 @pytest.mark.parametrize("pk", range(len(PARAM_GRID)))
-@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("path", EARLIER_PATHS)
 def test_realistic_within_path_bar(real, path, pk):
-    D, p = real, PARAM_GRID[pk]
+    check_realistic(real, path, pk)
+
+
+def check_realistic(D, path, pk):
+    """within the path's bar of the double-double reference: strip_bound on the NPS_FMT_GT2X paths, f64_bound elsewhere"""
+    p = PARAM_GRID[pk]
     co = D.co
     d = dict(kind=np.zeros(D.m, np.int32), rie=co["rie"], beta=co["beta"], eaf=co["eaf"], params=p, offset=0.0)
     dos = er.codes_dosages(D.codes)
     hi, lo, ab, nl, Dm, b, over = er.dd_reference(dos, co["beta"], co["eaf"], co["rie"], p)
+    assert not refused(path, d, lambda: PATHS[path](D, d), path), path + ": a realistic definition no path refuses"
     got, nloci, _ = PATHS[path](D, d)
     assert nloci == nl
     ok = np.isfinite(got)
