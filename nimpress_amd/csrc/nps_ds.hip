@@ -9,26 +9,18 @@
 // tree.  Both are deterministic and differ from the reference's sequential sums in the last bits.
 #include <algorithm>
 
-#include "nps_kernels.h"
+#include "nps_ds_common.h"
 
 namespace nps {
 
-static __device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-static __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// one 256-thread block per row
-__global__ __launch_bounds__(256) void ds_tally_kernel(const float *__restrict__ ds,
-                                                       uint64_t stride_f, uint64_t n,
-                                                       const nps_row_desc *__restrict__ desc,
-                                                       uint64_t n_rows, DsTally *__restrict__ out) {
+// The subset run's tally (nps_score_cohort_def_subset): ds_tally_kernel<float, false> (nps_ds_common.h) under a sample mask,
+// the one remaining copy of its summation tree.  A dropped sample adds neither to nmiss nor to the sum; a thread adds its
+// kept terms in the order that kernel adds them, and the wave and block combine is that kernel's: with every sample kept
+// the sum has the same bits.  bits: one bit per sample (nps_subset_mask.h); the four samples of a 16-byte load share a
+// nibble.
+__global__ __launch_bounds__(256) void ds_tally_masked_kernel(const float *__restrict__ ds, uint64_t stride_f, uint64_t n,
+                                                              const nps_row_desc *__restrict__ desc, uint64_t n_rows,
+                                                              const uint32_t *__restrict__ bits, DsTally *__restrict__ out) {
     __shared__ double s_sum[4];
     __shared__ uint32_t s_cnt[4];
     const uint64_t row = blockIdx.x;
@@ -38,11 +30,12 @@ __global__ __launch_bounds__(256) void ds_tally_kernel(const float *__restrict__
     const uint64_t n4 = (n + 3) / 4;  // rows are zero padded to a multiple of 64 floats
     uint32_t cnt = 0;
     double sum = 0.0;
-    auto take = [&](const float4 q, uint64_t v) {
+    auto nibble = [&](uint64_t v) { return (bits[v >> 3] >> (4 * (uint32_t)(v & 7))) & 15u; };  // (v < n4: word v / 8 < ceil(n / 32))
+    auto take = [&](const float4 q, uint32_t nib, uint64_t v) {
         const float e[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if (v * 4 + k < n) {
+            if (v * 4 + k < n && ((nib >> k) & 1u)) {
                 if (isnan(e[k]))
                     cnt += 1;
                 else
@@ -50,16 +43,27 @@ __global__ __launch_bounds__(256) void ds_tally_kernel(const float *__restrict__
             }
         }
     };
-    // 8 independent 16-byte loads in flight per thread (the per-thread sum order stays v-ascending)
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    // 8 independent 16-byte loads in flight per thread (the per-thread sum order stays v-ascending); the 1 KiB a wave
+    // loads at a time is not read when none of its 256 samples is kept (a wave-uniform decision)
     uint64_t v = threadIdx.x;
     for (; v + 7 * 256 < n4; v += 8 * 256) {
         float4 q[8];
+        uint32_t nib[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = p[v + u * 256];
+        for (int u = 0; u < 8; ++u) nib[u] = nibble(v + u * 256);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) take(q[u], v + u * 256);
+        for (int u = 0; u < 8; ++u) {
+            q[u] = zero;
+            if (__any(nib[u] != 0u)) q[u] = p[v + u * 256];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) take(q[u], nib[u], v + u * 256);
     }
-    for (; v < n4; v += 256) take(p[v], v);
+    for (; v < n4; v += 256) {
+        const uint32_t nib = nibble(v);
+        take(p[v], nib, v);
+    }
     sum = wave_sum_f64(sum);
     cnt = wave_sum_u32(cnt);
     const int w = threadIdx.x >> 6;
@@ -93,13 +97,7 @@ __global__ __launch_bounds__(256) void ds_params_kernel(const DsTally *__restric
         const bool flip = desc[row].ref_is_effect == 1;            // dosage = 2 - DS
         const RowDecision d = decide_row(p, over_maxmis(nmiss, n_samples, p.max_missing_rate), eaf, rie, neff, ngen);
         used = d.used;
-        DsRowP r;
-        r.beta = beta;
-        r.imp = d.mode == 1 ? d.imp : 0.0;
-        r.cst = d.mode == 2 ? d.imp : 0.0;
-        r.mode = d.mode;
-        r.rie = flip ? 1 : 0;
-        rowp[row] = r;
+        rowp[row] = ds_row_record(d, beta, flip);
         if (stats) stats[row] = row_stat(d, ngen, nmiss, neff);
     }
     const int cnt = __syncthreads_count(used);
@@ -206,13 +204,6 @@ hipError_t launch_decode_gt_to_ds(hipStream_t st, const void *d_gts, int elem_by
 }
 
 // device copy of ref_synth_ds (oracle/refcpu.c)
-static __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(256) void synth_ds_kernel(float *__restrict__ ds, uint64_t stride_f,
                                                        uint64_t n, uint64_t row0, uint64_t gen_row0,
                                                        uint64_t seed,
@@ -293,8 +284,7 @@ __global__ __launch_bounds__(256) void ds16_unpack_kernel(const uint16_t *__rest
     const uint16_t *in = src + (uint64_t)blockIdx.x * src_stride_e;
     float *out = dst + (uint64_t)blockIdx.x * dst_stride_f;
     for (uint64_t i = threadIdx.x; i < n; i += 256) {
-        const uint32_t k = in[i];
-        out[i] = k == 0xffffu ? __int_as_float(0x7fc00000) : ds16_value(k);
+        out[i] = DsElem<uint16_t>::value(in[i]);
     }
 }
 
@@ -329,13 +319,16 @@ hipError_t launch_ds16_unpack(hipStream_t st, const uint16_t *d_src, uint64_t sr
 }
 
 // ---- launchers --------------------------------------------------------------------------------
-hipError_t launch_ds_tally(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n,
-                           const nps_row_desc *d_desc, uint64_t n_rows, DsTally *d_tally) {
+hipError_t launch_ds_tally(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n, const nps_row_desc *d_desc,
+                           uint64_t n_rows, const uint32_t *d_bits, DsTally *d_tally) {
     if (n_rows == 0) return hipSuccess;
     if (n_rows > 0x7fffffffull) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(ds_tally_kernel, dim3((uint32_t)n_rows), dim3(256), 0, st, d_ds, stride_f, n,
-                       d_desc, n_rows, d_tally);
+    const dim3 grid((uint32_t)n_rows), block(256);
+    if (d_bits)
+        hipLaunchKernelGGL(ds_tally_masked_kernel, grid, block, 0, st, d_ds, stride_f, n, d_desc, n_rows, d_bits, d_tally);
+    else  // (nps_ds_common.h)
+        hipLaunchKernelGGL((ds_tally_kernel<float, false>), grid, block, 0, st, d_ds, stride_f, n, d_desc, n_rows, d_tally);
     return hipGetLastError();
 }
 

@@ -546,7 +546,7 @@ static int run_batch(nps_ctx *c) {
         {
             ProfScope ps(c, P_TALLY);
             HIP_TRY(launch_ds_tally(c->stream.get(), c->d_ds.get(), c->ds_stride_f, c->n, c->d_ds_desc.get(), drows,
-                                    c->d_ds_tally.get()));
+                                    nullptr, c->d_ds_tally.get()));
         }
         {
             ProfScope ps(c, P_PARAMS);
@@ -1834,7 +1834,7 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
                 HIP_TRY(launch_mx_tally_masked(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, set->d_unit.get(),
                                                c->d_rtally.get()));
             else
-                HIP_TRY(launch_mx_tally(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, c->n, c->d_rtally.get()));
+                HIP_TRY(launch_mx_tally(c->stream.get(), mxp, r.d_units, r.n_sb_cohort, r.sb0, c->d_rtally.get()));
         }
         hipError_t fe;
         {
@@ -1905,12 +1905,8 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         const uint64_t k = std::min(block_rows, m - r0);
         {
             ProfScope ps(c, P_TALLY);
-            if (set)
-                HIP_TRY(launch_ds_tally_masked(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0, k,
-                                               set->d_bits.get(), c->d_rds_tally.get() + r0));
-            else
-                HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0,
-                                        k, c->d_rds_tally.get() + r0));
+            HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0, k,
+                                    set ? set->d_bits.get() : nullptr, c->d_rds_tally.get() + r0));
         }
         {
             ProfScope ps(c, P_PARAMS);
@@ -2326,7 +2322,7 @@ static int mx_keep_tallies_locked(nps_cohort *c) {
                 while (e < n_sb && !mx_tallies_valid(c, e, 1)) ++e;
                 HIP_TRY(hipMemsetAsync(c->d_mx_row_tally.get() + sb * 128, 0, sizeof(unsigned long long) * (e - sb) * 128, nullptr));
                 mp.n_sb = (uint32_t)(e - sb);
-                HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data.get(), n_sb, sb, c->n_samples, c->d_mx_row_tally.get() + sb * 128));
+                HIP_TRY(launch_mx_tally(nullptr, mp, c->d_data.get(), n_sb, sb, c->d_mx_row_tally.get() + sb * 128));
                 sb = e;
             }
             HIP_TRY(hipDeviceSynchronize());

@@ -173,8 +173,9 @@ static inline uint64_t ds_stride_floats(uint64_t n_samples) {
     uint64_t w = n_samples ? n_samples : 1;
     return (w + 63) / 64 * 64;
 }
-hipError_t launch_ds_tally(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n,
-                           const nps_row_desc *d_desc, uint64_t n_rows, DsTally *d_tally);
+// d_bits: nullptr = every sample; else one bit per sample, ceil(n / 32) words (nps_subset_mask.h): the kept samples' tallies
+hipError_t launch_ds_tally(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n, const nps_row_desc *d_desc,
+                           uint64_t n_rows, const uint32_t *d_bits, DsTally *d_tally);
 hipError_t launch_ds_params(hipStream_t st, const DsTally *d_tally, const nps_row_desc *d_desc,
                             uint64_t n_rows, uint64_t n_samples, DevParams p, DsRowP *d_rowp,
                             nps_locus_stat *d_stats, unsigned long long *d_nloci);
@@ -218,6 +219,13 @@ hipError_t launch_synth_ds(hipStream_t st, float *d_ds, uint64_t stride_f, uint6
 static __device__ __forceinline__ float ds16_value(uint32_t k) {
     const float a = (float)k;
     return __fmaf_rn(a, 9.999999747378752e-05f, a * 2.5262125290942405e-12f);
+}
+// the splitmix64 finaliser of the synthetic generators: device copy of ref_mix64 (oracle/refcpu.c)
+static __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
 #endif
 // NPS_FMT_DS16 (2 bytes per genotype: k = dosage x 10^4, 0xFFFF = missing): the generator (device copy of ref_synth_ds16),
@@ -358,7 +366,7 @@ struct MxRun {
 hipError_t launch_fused_mx(hipStream_t st, const MxPlan &plan, const MxRun &r);
 // plan.given only: the whole-row tallies of the run's rows into d_tally (zero on entry), one read of the matrix
 hipError_t launch_mx_tally(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, unsigned long long *d_tally);
+                           unsigned long long *d_tally);
 // nps_mxg.hip: the run with its row tallies GIVEN (plan.given): per-row decisions + operands, then an ordinary grid of
 // P x Q workgroups
 hipError_t launch_mx_given(hipStream_t st, const MxPlan &plan, const MxRun &r);
@@ -382,14 +390,11 @@ hipError_t launch_gt2x_to_rows(hipStream_t st, const void *d_units, uint64_t n_s
 hipError_t launch_fill_gt2x_from_gt2(hipStream_t st, const uint32_t *d_src, uint64_t stride_words, uint64_t n_samples,
                                      uint64_t n_rows, void *d_units, unsigned long long *d_tally);
 
-// ---- a subset of a resident cohort's samples (nps_subset.hip; the mask: nps_subset_mask.h) -----------------------------
+// ---- a subset of a resident cohort's samples (nps_subset.hip; the mask: nps_subset_mask.h; dosage rows: launch_ds_tally) ----
 // launch_mx_tally under a mask: d_unit_mask holds one 64-bit word per unit of the cohort (sample s of the unit in bits
 // 2s, 2s + 1); the same tally words, counted over the kept samples
 hipError_t launch_mx_tally_masked(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
                                   const unsigned long long *d_unit_mask, unsigned long long *d_tally);
-// launch_ds_tally under a mask: d_bits holds one bit per sample, ceil(n / 32) words
-hipError_t launch_ds_tally_masked(hipStream_t st, const float *d_ds, uint64_t stride_f, uint64_t n, const nps_row_desc *d_desc,
-                                  uint64_t n_rows, const uint32_t *d_bits, DsTally *d_tally);
 // d_out[position of i among the kept samples] = d_scores[i] for every kept sample i < n
 hipError_t launch_subset_gather(hipStream_t st, const double *d_scores, uint64_t n, const uint32_t *d_bits,
                                 const uint32_t *d_prefix, double *d_out);

@@ -537,12 +537,6 @@ hipError_t launch_finish(hipStream_t st, const double *d_part, uint32_t n_chunks
 // ------------------------------------------------------------------------------------------
 // synthetic cohort generator -- device copy of ref_synth_code (oracle/refcpu.c); the two must
 // produce identical codes (tests/test_gpu_parity.py::test_synth_matches_oracle).
-static __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __global__ __launch_bounds__(256) void synth_gt_kernel(uint32_t *__restrict__ codes,
                                                        uint64_t stride_words, uint64_t n_samples,

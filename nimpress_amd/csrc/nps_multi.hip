@@ -43,12 +43,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------------------------------
 // packing: synthetic generator, converter from the 2-bit row-major cohort layout, tallies
-static __device__ __forceinline__ uint64_t mmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // NPS_CODE_* (0, 1, 3 = dosage 2, 2 = missing) -> layout code (0, 1, 2, 3 = missing)
 static __device__ __forceinline__ uint32_t m_code(uint32_t c) { return c ^ (c >> 1); }
@@ -75,8 +69,8 @@ __global__ __launch_bounds__(256) void synth_gt2m_kernel(uint4 *__restrict__ uni
             for (int j = 0; j < 16; ++j) {
                 const uint64_t r = sb * 128 + 32 * rq + 16 * (w & 1) + j;  // row relative to the first row written
                 if (r < n_rows && s < n_samples) {
-                    const uint64_t key = mmix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
-                    const uint64_t hsh = mmix64(key + s);
+                    const uint64_t key = mix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
+                    const uint64_t hsh = mix64(key + s);
                     const uint32_t gq = (uint32_t)hsh, ms = (uint32_t)(hsh >> 32);
                     const uint32_t c = ms < t_miss[r] ? NPS_CODE_MISSING
                                                       : (gq < t_hom[r] ? NPS_CODE_DOSAGE2 : (gq < t_het[r] ? 1u : 0u));
@@ -98,14 +92,14 @@ __global__ __launch_bounds__(256) void synth_tally_kernel(unsigned long long *__
                                                           const uint32_t *__restrict__ t_miss) {
     __shared__ uint32_t red[8];
     const uint64_t r = blockIdx.y;
-    const uint64_t key = mmix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
+    const uint64_t key = mix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
     const uint32_t th = t_het[r], tm = t_hom[r], tmi = t_miss[r];
     uint32_t nm = 0, ne = 0;
     const uint64_t s0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
     for (int k = 0; k < 16; ++k) {
         const uint64_t s = s0 + k;
         if (s < n_samples) {
-            const uint64_t hsh = mmix64(key + s);
+            const uint64_t hsh = mix64(key + s);
             const uint32_t gq = (uint32_t)hsh, ms = (uint32_t)(hsh >> 32);
             if (ms < tmi)
                 nm += 1;

@@ -1,7 +1,7 @@
 // nps_multi_ds.hip -- several score definitions over a resident dosage cohort (NPS_FMT_DS32 / NPS_FMT_DS16) in TWO reads of
 // the genotypes whatever the number of scores (reference loop nimpress.nim:634-641 run S times: S reads).
 //
-//   read 1  multi_ds_tally_kernel   per cohort row: nmissing, sum DS and sum (2 - DS) over the non-missing samples -- the
+//   read 1  ds_tally_kernel<E, true> per cohort row: nmissing, sum DS and sum (2 - DS) over the non-missing samples -- the
 //                                   tallies are the row's, not a score's: definitions may disagree about the effect allele
 //           multi_ds_params_kernel  per (score, row): the decision chain of getImputedDosages (nps_row_decision.h) on the
 //                                   sum the score's effect allele asks for -> one wave-uniform record
@@ -14,93 +14,9 @@
 // built with -ffp-contract=off: the multiply and the add of a term stay two operations, as in the reference.
 #include <algorithm>
 
-#include "nps_kernels.h"
+#include "nps_ds_common.h"
 
 namespace nps {
-
-static __device__ __forceinline__ double mds_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-static __device__ __forceinline__ uint32_t mds_wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// four neighbouring samples of a row as they lie in memory, and the float32 dosage an element stands for
-template <typename E>
-struct MdsElem;
-template <>
-struct MdsElem<float> {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ float value(float e) { return e; }
-};
-template <>
-struct MdsElem<uint16_t> {  // NPS_FMT_DS16: k = dosage x 10^4, 0xFFFF = missing (ds16_value: nps_kernels.h)
-    typedef unsigned short v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ float value(unsigned short k) {
-        return k == 0xffffu ? __int_as_float(0x7fc00000) : ds16_value(k);
-    }
-};
-
-// One 256-thread block per row, the shape of ds_tally_kernel (nps_ds.hip): thread t takes the lanes-of-four t, t + 256, ..
-// in ascending order, then the wave sum, then ((s0 + s1) + s2) + s3 -- so both sums have the bits of the neffect that
-// kernel gives the row with ref_is_effect 0 and 1.
-template <typename E>
-__global__ __launch_bounds__(256) void multi_ds_tally_kernel(const E *__restrict__ ds, uint64_t stride_e, uint64_t n,
-                                                             uint64_t n_rows, MultiDsTally *__restrict__ out) {
-    typedef typename MdsElem<E>::v4 V4;
-    __shared__ double s_sum[4], s_flp[4];
-    __shared__ uint32_t s_cnt[4];
-    const uint64_t row = blockIdx.x;
-    if (row >= n_rows) return;
-    const V4 *p = reinterpret_cast<const V4 *>(ds + row * stride_e);
-    const uint64_t n4 = (n + 3) / 4;  // rows are zero padded to a multiple of 64 elements
-    uint32_t cnt = 0;
-    double sum = 0.0, flp = 0.0;
-    auto take = [&](const V4 q, uint64_t v) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float e = MdsElem<E>::value(q[k]);
-            if (v * 4 + k < n) {
-                if (isnan(e)) {
-                    cnt += 1;
-                } else {
-                    sum += (double)e;
-                    flp += 2.0 - (double)e;
-                }
-            }
-        }
-    };
-    uint64_t v = threadIdx.x;
-    for (; v + 7 * 256 < n4; v += 8 * 256) {
-        V4 q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = p[v + u * 256];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) take(q[u], v + u * 256);
-    }
-    for (; v < n4; v += 256) take(p[v], v);
-    sum = mds_wave_sum_f64(sum);
-    flp = mds_wave_sum_f64(flp);
-    cnt = mds_wave_sum_u32(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[w] = sum;
-        s_flp[w] = flp;
-        s_cnt[w] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        MultiDsTally t;
-        t.nmiss = (unsigned long long)s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        t.sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-        t.sum_flipped = ((s_flp[0] + s_flp[1]) + s_flp[2]) + s_flp[3];
-        out[row] = t;
-    }
-}
 
 // one thread per (score = blockIdx.y, row).  ref_is_effect as in ds_params_kernel: == 1 flips the dosage (and takes the
 // flipped sum), bit 0 alone selects the homref imputation value (NPS_RIE_COUNTS_EFFECT: the row counts the effect allele).
@@ -126,13 +42,8 @@ __global__ __launch_bounds__(256) void multi_ds_params_kernel(const MultiDsTally
             dec = no_data_row(p, d.kind, d.eaf, rie);
         }
         used = dec.used;
-        DsRowP r;
-        r.beta = dec.mode ? d.beta : 0.0;  // (mode 0 adds 0 x 0: multi_ds_accumulate_kernel has no branch)
-        r.imp = dec.mode == 1 ? dec.imp : 0.0;
-        r.cst = dec.mode == 2 ? dec.imp : 0.0;
-        r.mode = dec.mode;
-        r.rie = flip ? 1 : 0;
-        rowp[row * (uint64_t)S + s] = r;
+        // (mode 0 adds 0 x 0: multi_ds_accumulate_kernel has no branch)
+        rowp[row * (uint64_t)S + s] = ds_row_record(dec, dec.mode ? d.beta : 0.0, flip);
     }
     const int cnt = __syncthreads_count(used);
     if (threadIdx.x == 0 && cnt) atomicAdd(&state[s].nloci, (unsigned long long)cnt);
@@ -151,7 +62,7 @@ __global__ __launch_bounds__(256) void multi_ds_accumulate_kernel(const E *__res
                                                                   const DsRowP *__restrict__ rowp_all, uint64_t n_rows_all,
                                                                   uint64_t rows_per_chunk, double *__restrict__ planes,
                                                                   uint64_t plane_stride) {
-    typedef typename MdsElem<E>::v4 V4;
+    typedef typename DsElem<E>::v4 V4;
     const uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const uint64_t r_begin = (uint64_t)blockIdx.y * rows_per_chunk;
     if (i >= n || r_begin >= n_rows_all) return;
@@ -168,7 +79,7 @@ __global__ __launch_bounds__(256) void multi_ds_accumulate_kernel(const E *__res
         uint64_t nan[4];  // the wave's lanes whose sample k is missing
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = MdsElem<E>::value(q[k]);
+            const float e = DsElem<E>::value(q[k]);
             nan[k] = __builtin_amdgcn_ballot_w64(isnan(e));
             dp[k] = (double)e;
             df[k] = 2.0 - dp[k];
@@ -248,12 +159,15 @@ hipError_t launch_multi_ds_tally(hipStream_t st, const void *d_ds, int elem_byte
     if (n_rows == 0) return hipSuccess;
     if (n_rows > 0x7fffffffull || (elem_bytes != 2 && elem_bytes != 4)) return hipErrorInvalidValue;
     (void)hipGetLastError();
+    // ds_tally_kernel (nps_ds_common.h) with both sums side by side: they have the bits of the neffect the single-score
+    // paths give the row with ref_is_effect 0 and 1, because they come from the same kernel text
+    const dim3 grid((uint32_t)n_rows), block(256);
     if (elem_bytes == 4)
-        hipLaunchKernelGGL(multi_ds_tally_kernel<float>, dim3((uint32_t)n_rows), dim3(256), 0, st, (const float *)d_ds,
-                           stride_e, n, n_rows, d_tally);
+        hipLaunchKernelGGL((ds_tally_kernel<float, true>), grid, block, 0, st, (const float *)d_ds, stride_e, n, nullptr, n_rows,
+                           d_tally);
     else
-        hipLaunchKernelGGL(multi_ds_tally_kernel<uint16_t>, dim3((uint32_t)n_rows), dim3(256), 0, st, (const uint16_t *)d_ds,
-                           stride_e, n, n_rows, d_tally);
+        hipLaunchKernelGGL((ds_tally_kernel<uint16_t, true>), grid, block, 0, st, (const uint16_t *)d_ds, stride_e, n, nullptr,
+                           n_rows, d_tally);
     return hipGetLastError();
 }
 

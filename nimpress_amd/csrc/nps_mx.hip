@@ -175,21 +175,11 @@ static __device__ __forceinline__ void mx_body(const MxArgs &a, char *const smem
             if (full || u < n_my) dst[u] = load_unit(k, u, sp);
     };
 
-    // tallyAlleles over the wave's units of a superblock: a lane holds rows 2*lane, 2*lane+1 (32 samples each) of
-    // every unit.  Codes 01 / 10 / 11 = dosage 1 / dosage 2 / missing: with X = set bits, Y = set high bits,
-    // Z = missing,  effect alleles = X + Y - 3 Z.
-    struct Tal {
-        uint32_t xa = 0, ya = 0, za = 0, xb = 0, yb = 0, zb = 0;
-    };
+    // tallyAlleles over the wave's units of a superblock (mx_tally_unit, nps_mx_common.h)
+    typedef MxTal Tal;
     auto tally_unit = [&](Tal &t, const v4u w) {
         if ((DBG & 1) || GIVEN) return;
-        const uint32_t sx = w.x >> 1, sy = w.y >> 1, sz = w.z >> 1, sw = w.w >> 1;
-        t.xa = bcnt_acc(w.y, bcnt_acc(w.x, t.xa));
-        t.ya = bcnt_acc((w.x & 0xAAAAAAAAu) | (sy & 0x55555555u), t.ya);
-        t.za = bcnt_acc((w.x & sx & 0x55555555u) | ((w.y & sy & 0x55555555u) << 1), t.za);
-        t.xb = bcnt_acc(w.w, bcnt_acc(w.z, t.xb));
-        t.yb = bcnt_acc((w.z & 0xAAAAAAAAu) | (sw & 0x55555555u), t.yb);
-        t.zb = bcnt_acc((w.z & sz & 0x55555555u) | ((w.w & sw & 0x55555555u) << 1), t.zb);
+        mx_tally_unit(t, w);
     };
     auto tally_add = [&](uint32_t kt, const Tal &t) {
         if (GIVEN) return;
@@ -617,39 +607,19 @@ __global__ __launch_bounds__(256) void mx_tally_kernel(const v4u *__restrict__ u
     const uint32_t sb = blockIdx.x, grp = blockIdx.y;
     if (tid < 128) s_eff[tid] = s_mis[tid] = 0u;
     __syncthreads();
-    uint32_t xa = 0, ya = 0, za = 0, xb = 0, yb = 0, zb = 0;
+    MxTal t;
     const uint32_t s_end = min(P, grp * 16 + 16);
     for (uint32_t strip = grp * 16; strip < s_end; ++strip) {
         const uint32_t nu = strip == P - 1 ? nu_last : 64u;
         const v4u *base = units + ((uint64_t)strip * 64 * n_sb_cohort + (uint64_t)(sb0 + sb) * nu) * 64 + lane;
         for (uint32_t u = wave; u < nu; u += 4) {
-            const v4u w = __builtin_nontemporal_load(base + (uint64_t)u * 64);
-            const uint32_t sx = w.x >> 1, sy = w.y >> 1, sz = w.z >> 1, sw = w.w >> 1;
-            xa = bcnt_acc(w.y, bcnt_acc(w.x, xa));
-            ya = bcnt_acc((w.x & 0xAAAAAAAAu) | (sy & 0x55555555u), ya);
-            za = bcnt_acc((w.x & sx & 0x55555555u) | ((w.y & sy & 0x55555555u) << 1), za);
-            xb = bcnt_acc(w.w, bcnt_acc(w.z, xb));
-            yb = bcnt_acc((w.z & 0xAAAAAAAAu) | (sw & 0x55555555u), yb);
-            zb = bcnt_acc((w.z & sz & 0x55555555u) | ((w.w & sw & 0x55555555u) << 1), zb);
+            mx_tally_unit(t, __builtin_nontemporal_load(base + (uint64_t)u * 64));
         }
     }
-    atomicAdd(&s_eff[2 * lane], xa + ya - 3u * za);
-    atomicAdd(&s_mis[2 * lane], za);
-    atomicAdd(&s_eff[2 * lane + 1], xb + yb - 3u * zb);
-    atomicAdd(&s_mis[2 * lane + 1], zb);
-    __syncthreads();
-    if (tid < 128)
-        atomicAdd(&tally[(uint64_t)sb * 128 + tid], ((unsigned long long)s_mis[tid] << 28) | (unsigned long long)s_eff[tid]);
+    mx_tally_commit(t, s_eff, s_mis, tally + (uint64_t)sb * 128);
 }
 
 // ---- packing: generator, plain rows <-> units -------------------------------------------------------------
-static __device__ __forceinline__ uint64_t xmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // one thread = one row of one unit (32 samples); block = 128 rows x 2 units; grid = (unit pairs, superblocks)
 __global__ __launch_bounds__(256) void synth_gt2x_kernel(unsigned long long *__restrict__ units, uint64_t n_units,
                                                          uint64_t n_sb, uint64_t n_samples, uint64_t sb0,
@@ -664,12 +634,12 @@ __global__ __launch_bounds__(256) void synth_gt2x_kernel(unsigned long long *__r
     const uint64_t r = sb * 128 + rho;  // row relative to the first row written = index into the thresholds
     unsigned long long out = 0;
     if (r < n_rows) {
-        const uint64_t key = xmix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
+        const uint64_t key = mix64(seed ^ ((gen_row0 + r) * 0xD1B54A32D192ED03ull));
         const uint32_t th = t_het[r], tm = t_hom[r], tmi = t_miss[r];
         for (int k = 0; k < 32; ++k) {
             const uint64_t s = unit * 32 + k;
             if (s < n_samples) {
-                const uint64_t h = xmix64(key + s);
+                const uint64_t h = mix64(key + s);
                 const uint32_t gq = (uint32_t)h, ms = (uint32_t)(h >> 32);
                 const unsigned long long c = ms < tmi ? 3ull : (gq < tm ? 2ull : (gq < th ? 1ull : 0ull));
                 out |= c << (2 * k);
@@ -889,8 +859,7 @@ hipError_t mx_plan(int device, uint64_t n_samples, uint64_t n_rows, bool two_pas
 }
 
 hipError_t launch_mx_tally(hipStream_t st, const MxPlan &plan, const void *d_units, uint64_t n_sb_cohort, uint64_t sb0,
-                           uint64_t n_samples, unsigned long long *d_tally) {
-    (void)n_samples;
+                           unsigned long long *d_tally) {
     (void)hipGetLastError();
     const uint32_t groups = (plan.P + 15) / 16;
     for (uint32_t s = 0; s < plan.n_sb; s += 1u << 30) {  // (grid.x holds 2^31 - 1 blocks)

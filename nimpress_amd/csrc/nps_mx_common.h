@@ -83,6 +83,35 @@ static __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) { 
     asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(x), "v"(acc));
     return d;
 }
+// tallyAlleles over units of the strip layout: a lane holds rows 2 lane (w.x, w.y) and 2 lane + 1 (w.z, w.w) of a unit,
+// 32 samples each.  Codes 01 / 10 / 11 = dosage 1 / dosage 2 / missing: with X = set bits, Y = set high bits,
+// Z = missing,  effect alleles = X + Y - 3 Z.
+struct MxTal {
+    uint32_t xa = 0, ya = 0, za = 0, xb = 0, yb = 0, zb = 0;
+};
+static __device__ __forceinline__ void mx_tally_unit(MxTal &t, const v4u w) {
+    const uint32_t sx = w.x >> 1, sy = w.y >> 1, sz = w.z >> 1, sw = w.w >> 1;
+    t.xa = bcnt_acc(w.y, bcnt_acc(w.x, t.xa));
+    t.ya = bcnt_acc((w.x & 0xAAAAAAAAu) | (sy & 0x55555555u), t.ya);
+    t.za = bcnt_acc((w.x & sx & 0x55555555u) | ((w.y & sy & 0x55555555u) << 1), t.za);
+    t.xb = bcnt_acc(w.w, bcnt_acc(w.z, t.xb));
+    t.yb = bcnt_acc((w.z & 0xAAAAAAAAu) | (sw & 0x55555555u), t.yb);
+    t.zb = bcnt_acc((w.z & sz & 0x55555555u) | ((w.w & sw & 0x55555555u) << 1), t.zb);
+}
+// end of the two tally kernels (mx_tally_kernel, mx_tally_masked_kernel; 256 threads): the four waves meet in s_eff /
+// s_mis ([128] each, zeroed behind a barrier by the caller), then one word (nmissing << 28 | neffect) per row is added to
+// the superblock's 128 tally words
+static __device__ __forceinline__ void mx_tally_commit(const MxTal &t, uint32_t *s_eff, uint32_t *s_mis,
+                                                       unsigned long long *__restrict__ tally_sb) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    atomicAdd(&s_eff[2 * lane], t.xa + t.ya - 3u * t.za);
+    atomicAdd(&s_mis[2 * lane], t.za);
+    atomicAdd(&s_eff[2 * lane + 1], t.xb + t.yb - 3u * t.zb);
+    atomicAdd(&s_mis[2 * lane + 1], t.zb);
+    __syncthreads();
+    if (tid < 128) atomicAdd(&tally_sb[tid], ((unsigned long long)s_mis[tid] << 28) | (unsigned long long)s_eff[tid]);
+}
+
 // where row r of a unit lives in its 1 KiB LDS image: a lane's two rows stay together (one ds_write_b128), and
 // the 32 lanes of a half wave read 256 different bytes in both transposed reads
 static __host__ __device__ inline int mx_rowoff(int r) {

@@ -1,5 +1,5 @@
-"""Scoring a chosen subset of a resident cohort's samples on NPS_FMT_DS32 cohorts (the masked ds_tally_kernel of
-nps_subset.hip), against the references run on the kept columns alone: statistics against the oracle's row loop
+"""Scoring a chosen subset of a resident cohort's samples on NPS_FMT_DS32 cohorts (ds_tally_masked_kernel,
+nps_ds.hip), against the references run on the kept columns alone: statistics against the oracle's row loop
 (refcpu.RefScorer.row_ds with n = n_kept: counts, used and reason exact, the float64 neffect as tests/test_gpu_parity.py
 compares it), scores against the double-double sums of tests/exact_reference.py within f64_bound, the bar
 tests/test_gpu_exact.py holds the dosage paths to.  Inputs and the assertion that the subset run decided differently from

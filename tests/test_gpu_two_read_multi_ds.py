@@ -112,26 +112,28 @@ def test_multi_ds_vs_oracle(shape, pk, fmt):
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_multi_ds_row_tallies_equal_the_streaming_path_bit_for_bit(fmt):
     """nmissing, sum and sum_flipped of a pass == nmissing / neffect of nps_flush for the same rows pushed with nps_push_ds,
-    ref_is_effect 0 and 1"""
-    n, m = 4099, 40
-    ds, descs = make_ds_case(n, m, 1, 7, fmt, with_kinds=False)
-    dev = upload(ds, fmt)
-    msc = capi.MultiScorer(n, capi.make_params(), 1)
-    mdef = capi.MultiDef(descs)
-    msc.score_cohort(dev, mdef)
-    nm, sm, sf = msc.row_tallies()
-    nm2, sm2, sf2 = msc.row_tallies(first=5, n=3)
-    assert np.array_equal(nm2, nm[5:8]) and np.array_equal(sm2, sm[5:8]) and np.array_equal(sf2, sf[5:8])
-    for rie, got in ((0, sm), (1, sf)):
-        sc = capi.Scorer(n, capi.make_params())
-        for j in range(m):
-            sc.push_ds(ds[j], rie, 0.01, 0.3)
-        st = sc.flush()
-        sc.close()
-        assert np.array_equal(st["nmissing"], nm)
-        assert np.array_equal(st["neffect"].view(np.int64), got.view(np.int64)), rie
-    for x in (msc, mdef, dev):
-        x.close()
+    ref_is_effect 0 and 1.  4 099 samples: the plain loop alone; 7 173: thread 0 alone takes one turn of the eight-fold
+    unrolled loop; 8 193: every thread does, and thread 0 a lane-of-four more"""
+    m = 40
+    for n in (4099, 7173, 8193):
+        ds, descs = make_ds_case(n, m, 1, 7, fmt, with_kinds=False)
+        dev = upload(ds, fmt)
+        msc = capi.MultiScorer(n, capi.make_params(), 1)
+        mdef = capi.MultiDef(descs)
+        msc.score_cohort(dev, mdef)
+        nm, sm, sf = msc.row_tallies()
+        nm2, sm2, sf2 = msc.row_tallies(first=5, n=3)
+        assert np.array_equal(nm2, nm[5:8]) and np.array_equal(sm2, sm[5:8]) and np.array_equal(sf2, sf[5:8])
+        for rie, got in ((0, sm), (1, sf)):
+            sc = capi.Scorer(n, capi.make_params())
+            for j in range(m):
+                sc.push_ds(ds[j], rie, 0.01, 0.3)
+            st = sc.flush()
+            sc.close()
+            assert np.array_equal(st["nmissing"], nm), n
+            assert np.array_equal(st["neffect"].view(np.int64), got.view(np.int64)), (n, rie)
+        for x in (msc, mdef, dev):
+            x.close()
 
 
 def test_multi_ds_column_is_independent_of_the_other_definitions():
