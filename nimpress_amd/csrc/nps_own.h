@@ -1,4 +1,5 @@
-// nps_own.h -- the owners of the HIP resources of nps_engine.hip (internal: not part of the C-ABI, no kernel sees it).
+// nps_own.h -- the owners of the HIP resources of the C-ABI's objects (internal: included through nps_engine.h by the four
+// units that implement them, not part of the C-ABI, no kernel sees it).
 //
 // Five move-only types, released by their destructors: a struct that holds them needs no list of frees, and a function
 // that holds one may return from anywhere.  Four hold one resource each; the fifth, StagingRing, is made of two of the

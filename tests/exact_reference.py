@@ -22,7 +22,7 @@ LOCUS = {"ps": 0, "homref": 1, "fail": 2, "ignore": 3}
 SAMPLE_INTERNAL = ("int_ps", "int_fail")
 CODE_DOSAGE = np.array([0.0, 1.0, np.nan, 2.0])   # 2-bit codes (tests/special_cases.py): 2 = missing
 FLUSH_SB = 1024                    # kFlushSb, nps_mx_route.h
-BAND_BITS, MAX_BANDS = 30, 8       # kMxBandBits, kMxMaxBands, nps_engine.hip:1469
+BAND_BITS, MAX_BANDS = 30, 8       # kMxBandBits, kMxMaxBands, nps_scale.h
 
 
 def gamma(k):
@@ -227,8 +227,8 @@ def f64_bound(ab, m_used, got, nloci):
 
 
 def strip_scale(beta, eaf):
-    """F of the fixed-point pass: bound = max |beta| (4 + max(2, 2 |eaf|)) < 2^e2, F = 56 - e2 (nps_engine.hip:1984-1990,
-    nps_engine.hip mx_special)"""
+    """F of the fixed-point pass: bound = max |beta| (4 + max(2, 2 |eaf|)) < 2^e2, F = 56 - e2 (nps_scale.h:
+    mx_scale_exponent of the bound mx_special gives a row)"""
     ie = np.maximum(2.0, 2.0 * np.abs(eaf))
     bound = float(np.max(np.abs(beta) * (4.0 + ie))) if beta.size else 0.0
     if bound <= 0.0:
@@ -238,7 +238,7 @@ def strip_scale(beta, eaf):
 
 def strip_bands(beta, eaf):
     """band of every row (0 for a zero beta) and the scale of every band, as nps_scoredef_create makes them
-    (nps_engine.hip:1539-1575)"""
+    (nps_scale.h: mx_band_plan; tests/test_weight_scale.py holds the two to each other)"""
     ie = np.maximum(2.0, 2.0 * np.abs(eaf))
     v = np.abs(beta) * (4.0 + ie)
     if not (v > 0).any():
@@ -534,7 +534,7 @@ def given_teams(n_strips, cus, n_sb):
 # digit probes over several magnitude bands, and under int_ps
 def banded_probe_betas(m, n_bands, seed, top=-4):
     """row j in band j % n_bands: full-mantissa betas in the binade [2^t_b, 2^(t_b + 1)), t_b = top - 30 b - 2 b (a
-    bound exponent 30 b + 1 .. 30 b + 3 below the top one: band b exactly, nps_engine.hip:1551)"""
+    bound exponent 30 b + 1 .. 30 b + 3 below the top one: band b exactly, nps_scale.h: mx_band_plan)"""
     rng = np.random.default_rng(seed)
     mant = rng.integers(0, 2 ** 52, m, dtype=np.int64) + 2 ** 52
     sign = np.where(rng.uniform(size=m) < 0.5, -1, 1)
@@ -578,7 +578,7 @@ def banded_probe_reference(codes, beta, eaf, rie, params, offset=0.0):
 # ------------------------------------------------------------------------------------------------------------------
 # the multi-score path (nps_multi.hip)
 def multi_scale(beta, eaf, ND):
-    """F[s] = 8 ND - 9 - e, bound = max |beta| (3 + max(2, 2 max |eaf|)) < 2^e (nps_engine.hip:2325-2329)"""
+    """F[s] = 8 ND - 9 - e, bound = max |beta| (3 + max(2, 2 max |eaf|)) < 2^e (nps_scale.h: multi_scale)"""
     bound = float(np.max(np.abs(beta))) * (3.0 + max(2.0, 2.0 * float(np.max(np.abs(eaf)))))
     return 8 * ND - 9 - (math.frexp(bound)[1] if bound > 0 else 0), bound
 

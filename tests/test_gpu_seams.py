@@ -1,6 +1,6 @@
 """Every host-side loop that cuts one C-ABI call into several kernel launches or staging chunks, crossed once.
 
-The other GPU modules pin the arithmetic; their shapes fit one launch and one chunk of every loop in nps_engine.hip,
+The other GPU modules pin the arithmetic; their shapes fit one launch and one chunk of every loop in nps_cohort.hip, nps_resident.hip,
 nps_kernels.hip, nps_mx.hip and nps_multi.hip (the generator's 32 768-row launches excepted).  Here each case is the smallest
 shape with rows on both sides of a SEAM -- the first row a second launch or chunk handles -- with a ragged second piece, so
 that a wrong second-chunk offset, a stage buffer that still holds the previous chunk, a code map indexed from the chunk
