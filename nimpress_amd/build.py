@@ -78,9 +78,12 @@ HOST_DIR = os.path.join(CSRC, "host")
 LIBHOST = os.path.join(PKG_DIR, "libnimpress_host.so")
 CLI = os.path.join(PKG_DIR, "nimpress")
 GXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wextra", "-ffp-contract=off"]
-# the host's translation units (the first two hold no libnps call: text and common parts, genotype file readers)
-HOST_SOURCES = ["nimpress_text.cpp", "nimpress_readers.cpp", "nimpress_scoring.cpp", "nimpress_hooks.cpp"]
-HOST_HEADERS = ["nimpress_host.hpp", "nimpress_internal.hpp"]
+# the genotype file reader units and the text / common parts: no libnps call, so they link on their own (what the
+# stand-alone reader drivers under tests/native are built from)
+HOST_READER_SOURCES = ["nimpress_text.cpp", "nimpress_bgzf.cpp", "nimpress_vcftext.cpp", "nimpress_bcf.cpp",
+                       "nimpress_plink.cpp", "nimpress_readers.cpp"]
+HOST_SOURCES = HOST_READER_SOURCES + ["nimpress_scoring.cpp", "nimpress_hooks.cpp"]
+HOST_HEADERS = ["nimpress_host.hpp", "nimpress_internal.hpp", "nimpress_readers.hpp"]
 
 
 def build_host(force: bool = False, verbose: bool = False) -> List[str]:

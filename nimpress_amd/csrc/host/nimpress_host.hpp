@@ -103,7 +103,7 @@ struct Variant {
     int32_t gtValue(size_t i) const;  // element i widened like bcf_get_genotypes does
 };
 
-struct IndexedSource;  // header + tabix / CSI index of an indexed file (nimpress_readers.cpp)
+struct IndexedSource;  // header + tabix / CSI bin index of an indexed file (opaque: nimpress_readers.cpp)
 
 struct VCF {
     std::vector<std::string> samples;

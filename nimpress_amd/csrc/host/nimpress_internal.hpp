@@ -1,6 +1,6 @@
 // nimpress_internal.hpp -- what the host's translation units share with each other and with nobody else
-// (nimpress_text.cpp, nimpress_readers.cpp, nimpress_scoring.cpp, nimpress_hooks.cpp).  The interface of the host is
-// nimpress_host.hpp; the functions declared here are not exported from libnimpress_host.so.
+// (nimpress_text.cpp, the reader units over nimpress_readers.hpp, nimpress_scoring.cpp, nimpress_hooks.cpp).  The interface
+// of the host is nimpress_host.hpp; the functions declared here are not exported from libnimpress_host.so.
 #pragma once
 #include "nimpress_host.hpp"
 

@@ -1,4 +1,5 @@
-// Test driver for the FORMAT/PL readers (no GPU, no libnps call: links nimpress_text.cpp + nimpress_readers.cpp only).
+// Test driver for the FORMAT/PL readers (no GPU, no libnps call: links the reader units of
+// nimpress_amd/build.py's HOST_READER_SOURCES only).
 //   pl_driver <file> [<file> ...]
 // opens every genotype file under NIMPRESS_FORMAT=PL (set here) and prints, per file, either
 //   refused <file>: <the reader's message>

@@ -2,7 +2,7 @@
 .pvar and .psam.  Test infrastructure, the twin of tests/bcfwriter.py.
 
 PARITY UNPINNED: neither plink2 nor the .pgen specification is in this image and the reference (which reads VCF/BCF
-only) holds no .pgen fixture, so the reader in nimpress_readers.cpp and this writer vouch for each other -- exactly as the
+only) holds no .pgen fixture, so the reader in nimpress_plink.cpp and this writer vouch for each other -- exactly as the
 BCF2/CSI reader and tests/bcfwriter.py do.  Layout as published for pgenlib: bytes 0-1 magic 0x6c 0x1b, byte 2 storage
 mode 0x02, uint32 variant count, uint32 sample count, one flag byte (0x40: every ALT allele "trusted"), then per
 variant ceil(N/4) bytes: sample i in bits 2(i mod 4) of byte i div 4, code = number of ALT alleles, 3 = missing."""

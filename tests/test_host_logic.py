@@ -367,95 +367,7 @@ def test_cli_surface():
     assert r.returncode == 1 and r.stdout.startswith("Usage:")
 
 
-# ------------------------------------------------------------------------------------------
-# BGZF + tabix writer (test-side) to exercise multi-block random access
-import struct
-import zlib
-
-
-def _bgzf_block(data: bytes) -> bytes:
-    c = zlib.compressobj(6, zlib.DEFLATED, -15)
-    comp = c.compress(data) + c.flush()
-    bsize = len(comp) + 25
-    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize)
-            + comp + struct.pack("<II", zlib.crc32(data), len(data)))
-
-
-def _reg2bin(beg, end):
-    end -= 1
-    for shift, off in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
-        if beg >> shift == end >> shift:
-            return off + (beg >> shift)
-    return 0
-
-
-def write_bgzf_vcf_with_tbi(path, header_lines, records):
-    """records: list of (contig, pos, ref, line) sorted by contig order of appearance, pos."""
-    out = bytearray()
-    buf = bytearray()
-    voffs = []
-
-    def flush():
-        nonlocal buf
-        if buf:
-            out.extend(_bgzf_block(bytes(buf)))
-            buf = bytearray()
-
-    def add_line(txt):
-        nonlocal buf
-        data = txt.encode() + b"\n"
-        start = (len(out) << 16) | len(buf)
-        i = 0
-        while i < len(data):
-            room = 0xff00 - len(buf)
-            if room == 0:
-                flush()
-                room = 0xff00
-            buf.extend(data[i:i + room])
-            i += room
-        if len(buf) >= 0xff00:
-            flush()
-        end = (len(out) << 16) | len(buf)
-        return start, end
-
-    for h in header_lines:
-        add_line(h)
-    contigs = []
-    index = {}
-    for contig, pos, ref, line in records:
-        vs, ve = add_line(line)
-        if contig not in index:
-            contigs.append(contig)
-            index[contig] = ({}, {})
-        bins, lin = index[contig]
-        beg, end = pos - 1, pos - 1 + len(ref)
-        bins.setdefault(_reg2bin(beg, end), []).append((vs, ve))
-        for w in range(beg >> 14, ((end - 1) >> 14) + 1):
-            lin[w] = min(lin.get(w, vs), vs)
-    flush()
-    out.extend(_bgzf_block(b""))
-    open(path, "wb").write(bytes(out))
-    names = b"".join(c.encode() + b"\0" for c in contigs)
-    t = bytearray(b"TBI\1" + struct.pack("<8i", len(contigs), 2, 1, 2, 0, ord("#"), 0, len(names)) + names)
-    for c in contigs:
-        bins, lin = index[c]
-        t += struct.pack("<i", len(bins))
-        for b, chunks in bins.items():
-            merged = [(chunks[0][0], chunks[-1][1])]
-            t += struct.pack("<Ii", b, len(merged))
-            for vs, ve in merged:
-                t += struct.pack("<QQ", vs, ve)
-        nw = max(lin) + 1 if lin else 0
-        t += struct.pack("<i", nw)
-        last = 0
-        for w in range(nw):
-            last = lin.get(w, last)
-            t += struct.pack("<Q", last)
-    tb = bytearray()
-    for i in range(0, len(t), 0xff00):
-        tb += _bgzf_block(bytes(t[i:i + 0xff00]))
-    tb += _bgzf_block(b"")
-    open(path + ".tbi", "wb").write(bytes(tb))
+from tbiwriter import write_bgzf_vcf_with_tbi  # noqa: E402  (BGZF + tabix writer, shared with test_reader_dump.py)
 
 
 def test_tabix_random_access_multi_block(host, tmp_path):
@@ -735,15 +647,15 @@ def test_ingest_under_sanitizers(tmp_path, san):
     import shutil
     import subprocess
     import bcfwriter
+    from nimpress_amd.build import HOST_READER_SOURCES
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("no g++")
     launcher = _tsan_launcher() if san == "thread" else []
     exe = str(tmp_path / "ingest")
     cmd = [gxx, "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=" + san, "-fno-omit-frame-pointer", "-o", exe,
-           os.path.join(ROOT, "tests", "native", "ingest_driver.cpp"),
-           os.path.join(ROOT, "nimpress_amd", "csrc", "host", "nimpress_text.cpp"),
-           os.path.join(ROOT, "nimpress_amd", "csrc", "host", "nimpress_readers.cpp"), "-lz"]
+           os.path.join(ROOT, "tests", "native", "ingest_driver.cpp")] + [
+               os.path.join(ROOT, "nimpress_amd", "csrc", "host", f) for f in HOST_READER_SOURCES] + ["-lz"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0 and "sanitize" in r.stderr:
         pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])

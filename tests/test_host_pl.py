@@ -261,9 +261,10 @@ def test_reader_errors_name_the_record(tmp_path, monkeypatch):
 # ------------------------------------------------------------------------------------------------------------------
 # the readers alone, under sanitizers
 def test_pl_readers_under_sanitizers(tmp_path):
-    """tests/native/pl_driver.cpp (its own main; nimpress_text.cpp + nimpress_readers.cpp, no libnps) built with
+    """tests/native/pl_driver.cpp (its own main; the reader units of build.HOST_READER_SOURCES, no libnps) built with
     -fsanitize=address,undefined on truncated PL fields, empty fields, a huge integer, short vectors, a wrong BCF length:
     a clean exit, no sanitizer report, the right values and the right refusals"""
+    from nimpress_amd.build import HOST_READER_SOURCES
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("no g++")
@@ -271,8 +272,8 @@ def test_pl_readers_under_sanitizers(tmp_path):
     hostdir = os.path.join(ROOT, "nimpress_amd", "csrc", "host")
     # (-O0: the build is most of this test's time, and the sanitizers need no more)
     cmd = [gxx, "-O0", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-o", exe, os.path.join(ROOT, "tests", "native", "pl_driver.cpp"),
-           os.path.join(hostdir, "nimpress_text.cpp"), os.path.join(hostdir, "nimpress_readers.cpp"), "-lz"]
+           "-fno-omit-frame-pointer", "-o", exe, os.path.join(ROOT, "tests", "native", "pl_driver.cpp")] + [
+               os.path.join(hostdir, f) for f in HOST_READER_SOURCES] + ["-lz"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0 and "sanitize" in r.stderr:
         pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
