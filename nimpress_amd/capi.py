@@ -24,6 +24,8 @@ FMT_GT2, FMT_DS32, FMT_GT2M, FMT_GT2X, FMT_GT_AUTO, FMT_DS16 = 0, 1, 2, 3, 4, 5
 ROW_NOT_IN_SCORE = 4
 RIE_COUNTS_EFFECT = 2   # dosage cohorts: the row already counts the effect allele (NPS_RIE_COUNTS_EFFECT)
 MULTI_MAX_SCORES = 8
+GROUPS_MAX = 8
+GROUP_NONE = 255        # a sample that belongs to no group (NPS_GROUP_NONE)
 MODE_AUTO, MODE_TWOPASS, MODE_FUSED = 0, 1, 2
 
 NPS_OK = 0
@@ -69,6 +71,9 @@ SYMBOLS = [
     "nps_push_pl", "nps_cohort_push_pl", "nps_pl_likelihoods",
     "nps_sampleset_create", "nps_sampleset_n_samples", "nps_sampleset_n_kept", "nps_sampleset_destroy",
     "nps_score_cohort_def_subset", "nps_finish_subset", "nps_finish_subset_device",
+    "nps_samplegroups_create", "nps_samplegroups_n_groups", "nps_samplegroups_n_samples", "nps_samplegroups_size",
+    "nps_samplegroups_destroy", "nps_score_cohort_def_groups", "nps_flush_groups", "nps_finish_groups",
+    "nps_finish_groups_device",
 ]
 
 
@@ -227,6 +232,18 @@ def load(with_torch: bool = True):
     L.nps_score_cohort_def_subset.argtypes = [vp, vp, u64, vp, vp]
     L.nps_finish_subset.argtypes = [vp, vp, dbl, vp, C.POINTER(u64)]
     L.nps_finish_subset_device.argtypes = [vp, vp, dbl, vp, C.POINTER(u64)]
+    L.nps_samplegroups_create.argtypes = [C.POINTER(vp), i32, u64, vp, i32]
+    L.nps_samplegroups_n_groups.argtypes = [vp]
+    L.nps_samplegroups_n_samples.argtypes = [vp]
+    L.nps_samplegroups_n_samples.restype = u64
+    L.nps_samplegroups_size.argtypes = [vp, i32]
+    L.nps_samplegroups_size.restype = u64
+    L.nps_samplegroups_destroy.argtypes = [vp]
+    L.nps_samplegroups_destroy.restype = None
+    L.nps_score_cohort_def_groups.argtypes = [vp, vp, u64, vp, vp]
+    L.nps_flush_groups.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.nps_finish_groups.argtypes = [vp, vp, dbl, vp, vp]
+    L.nps_finish_groups_device.argtypes = [vp, vp, dbl, vp, vp]
     L.nps_live_resources.argtypes = []
     L.nps_live_resources.restype = C.c_int64
     _lib = L
@@ -441,6 +458,37 @@ class SampleSet:
             pass
 
 
+class SampleGroups:
+    """A partition of a cohort's samples into groups (nps_samplegroups): labels[i] is the group of sample i, 0 .. n_groups - 1,
+    or GROUP_NONE.  Scorer.score_cohort_def_groups scores every group as if it were the whole cohort, in one pass."""
+
+    def __init__(self, labels, n_groups: int, device: int = 0):
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        assert labels.ndim == 1
+        self._h = C.c_void_p()
+        self.n_samples, self.device = int(labels.size), device
+        _check(load().nps_samplegroups_create(C.byref(self._h), device, labels.size, labels.ctypes.data if labels.size else None,
+                                              int(n_groups)))
+
+    @property
+    def n_groups(self) -> int:
+        return int(load().nps_samplegroups_n_groups(self._h))
+
+    def size(self, k: int) -> int:
+        return int(load().nps_samplegroups_size(self._h, int(k)))
+
+    def close(self):
+        if self._h:
+            load().nps_samplegroups_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Scorer:
     """computePolygenicScores (nimpress.nim:592-649) with the row loop on the GPU."""
 
@@ -448,6 +496,7 @@ class Scorer:
         self._h = C.c_void_p()
         self.n = int(n_samples)
         self.device = device
+        self._n_groups = 1      # of the groups object of the last grouped call (flush_groups' second axis)
         _check(load().nps_create(C.byref(self._h), device, self.n, C.byref(params)))
 
     # -- one call per score row, in score-file order
@@ -528,6 +577,41 @@ class Scorer:
         nloci = C.c_uint64(0)
         _check(load().nps_finish_subset_device(self._h, sset._h, float(offset), C.c_void_p(d_scores_ptr), C.byref(nloci)))
         return int(nloci.value)
+
+    def score_cohort_def_groups(self, cohort: Cohort, sdef: ScoreDef, groups: SampleGroups, row0: int = 0):
+        """score every group of `groups` as if it were the whole cohort, in one pass (nps_score_cohort_def_groups: FMT_DS32 and
+        FMT_DS16 cohorts); calls accumulate like score_cohort_def"""
+        _check(load().nps_score_cohort_def_groups(self._h, cohort._h, row0, sdef._h, groups._h))
+        self._n_groups = groups.n_groups
+
+    def flush_groups(self, n_groups: Optional[int] = None) -> np.ndarray:
+        """Completes the grouped rows; returns their stats, a structured array [rows, G] (nps_flush_groups); G is that of the
+        last grouped call unless n_groups says otherwise"""
+        out = []
+        while True:
+            cap = 65536
+            buf = np.zeros(cap, dtype=STAT_DTYPE)
+            n = C.c_size_t(0)
+            _check(load().nps_flush_groups(self._h, buf.ctypes.data, cap, C.byref(n)))
+            out.append(buf[: n.value])
+            if n.value < cap:
+                break
+        flat = np.concatenate(out)
+        G = int(n_groups) if n_groups else self._n_groups
+        return flat.reshape(-1, G)
+
+    def finish_groups(self, groups: SampleGroups, offset: float) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores[n] in cohort order -- NaN for a GROUP_NONE sample --, nloci[G]) -- nps_finish_groups"""
+        scores = np.empty(max(self.n, 1), dtype=np.float64)
+        nloci = np.zeros(GROUPS_MAX, dtype=np.uint64)
+        _check(load().nps_finish_groups(self._h, groups._h, float(offset), scores.ctypes.data, nloci.ctypes.data))
+        return scores[: self.n], nloci[: groups.n_groups].astype(np.int64)
+
+    def finish_groups_device(self, groups: SampleGroups, offset: float, d_scores_ptr: int) -> np.ndarray:
+        """every sample's score -> caller-allocated device buffer (n_samples float64); returns nloci[G]."""
+        nloci = np.zeros(GROUPS_MAX, dtype=np.uint64)
+        _check(load().nps_finish_groups_device(self._h, groups._h, float(offset), C.c_void_p(d_scores_ptr), nloci.ctypes.data))
+        return nloci[: groups.n_groups].astype(np.int64)
 
     def finish_device(self, offset: float, d_scores_ptr: int) -> int:
         """scores -> caller-allocated device buffer (n_samples float64); returns nloci."""

@@ -1,7 +1,7 @@
 // nps_engine.h -- what the units that implement the C-ABI of include/nps.h share (internal: no kernel source sees it).
 //
 // One unit per object: nps_engine.hip (errors, device selection, nps_ctx and everything streamed through it),
-// nps_cohort.hip (nps_cohort), nps_resident.hip (nps_scoredef, nps_sampleset, scoring a resident cohort) and
+// nps_cohort.hip (nps_cohort), nps_resident.hip (nps_scoredef, nps_sampleset, nps_samplegroups, scoring a resident cohort) and
 // nps_multiscore.hip (nps_multidef, nps_multi).  Here: the objects' structs, HIP_TRY, the one row path through a staging
 // ring with the checks of a pushed row (inline: a per-row push makes no call into another unit), and the declarations of
 // the helpers one unit has for the others -- hidden, so that the library exports what it did as one unit.
@@ -29,6 +29,7 @@ int check_params(const nps_params *p);
 DevParams dev_params(const nps_params &p);
 int check_usable(nps_ctx *c);
 int check_sampleset(const nps_ctx *c, const nps_sampleset *s);
+int check_ungrouped(const nps_ctx *c, const char *what);
 int ensure_all_chunks(nps_ctx *c);
 int run_batch(nps_ctx *c);
 int materialize_resident_stats(nps_ctx *c);
@@ -51,6 +52,10 @@ hipError_t upload_desc(DevBuf<nps_row_desc> &d, const nps_row_desc *rows, uint64
             return fail(_e == hipErrorOutOfMemory ? NPS_E_NOMEM : NPS_E_HIP, "%s failed: %s",  \
                         #expr, hipGetErrorString(_e));                                         \
     } while (0)
+
+// nps_ctx::d_nloci, the device's result block as nps_reset zeroes it and a grouped finish fetches it: [0] used rows, [1] status
+// bits, [kGroupNloci .. + 8) the rows used per group of a grouped context
+constexpr size_t kResultWords = 16, kGroupNloci = 8;
 
 enum ProfClass { P_DECODE = 0, P_TALLY, P_PARAMS, P_ACCUM, P_FUSED, P_REDUCE, P_COUNT };
 
@@ -116,6 +121,23 @@ struct nps_sampleset {
     }
 };
 
+// A partition of a cohort's samples into groups (nps_score_cohort_def_groups): the labels of nps_group_labels.h on the
+// device, immutable after creation -- contexts on several threads may share one.
+struct nps_samplegroups {
+    int device = 0;
+    int n_groups = 0;
+    uint64_t n_samples = 0;
+    uint64_t size[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<unsigned char> d_label;        // one byte per sample, padded with 255 to a multiple of 64 (tally, accumulation, finish)
+    DevBuf<unsigned char> d_present;      // one byte per 256 samples: the groups that occur there (the tally)
+    DevBuf<unsigned long long> d_size;    // [n_groups] (the rows' decisions)
+
+    ~nps_samplegroups() {  // queued work may still read the labels
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
+};
+
 struct PendingRow {
     int32_t batch_idx;  // >= 0: index into the open GT / DS batch's device stats; -1: host stat
     int32_t is_ds;      // which open batch batch_idx refers to
@@ -164,6 +186,14 @@ struct nps_ctx {
     // resident DS runs (grown on demand)
     DevBuf<DsTally> d_rds_tally;
     DevBuf<DsRowP> d_rds_rowp;
+    // grouped runs (nps_score_cohort_def_groups): the context is "grouped" from its first such call until nps_reset, with
+    // ONE groups object; plain_rows: it has taken ungrouped rows since its last reset (the two do not mix)
+    const nps_samplegroups *groups = nullptr;
+    bool plain_rows = false;
+    DevBuf<DsTally> d_grp_tally;          // [rows][n_groups]
+    DevBuf<GroupRowP> d_grp_rowp;         // [rows]
+    DevBuf<double> d_grp_imp;             // [rows][8]
+    DevBuf<nps_locus_stat> d_grp_stats;   // [rows][n_groups]; entries of a run wait here like d_rstats' (res_pending)
 
     StagingRing poly{2};  // raw GT records of ploidy > 2, read by the decode kernel (grows to the widest record pushed)
     StagingRing pl{4};    // FORMAT/PL vectors of nps_push_pl, read by decode_pl_kernel (grows to the widest record pushed)
@@ -177,7 +207,7 @@ struct nps_ctx {
     uint32_t chunks_used = 0;
     DevBuf<double> d_scores;
     DevBuf<double> d_subset_scores;          // nps_finish_subset: the kept samples' scores on their way to the host
-    DevBuf<unsigned long long> d_nloci;      // [0] used rows counted on the device, [1] sticky status bits
+    DevBuf<unsigned long long> d_nloci;      // [0] used rows counted on the device, [1] sticky status bits, [8 .. 15] per group
     unsigned long long *h_result = nullptr;  // pinned copy of that block
     bool broken = false;                     // a launch sequence failed half-way: nps_reset first
     double const_sum = 0.0;   // contributions of rows without genotype data (host decided)

@@ -114,7 +114,7 @@ static void choose_geometry(nps_ctx *c) {
 
 static int zero_state(nps_ctx *c) {
     // d_part is not touched: chunks_used = 0 makes the first writer overwrite it
-    HIP_TRY(hipMemsetAsync(c->d_nloci.get(), 0, 3 * sizeof(unsigned long long), c->stream.get()));
+    HIP_TRY(hipMemsetAsync(c->d_nloci.get(), 0, kResultWords * sizeof(unsigned long long), c->stream.get()));
     if (c->gt.rows)  // tallies of rows decoded into the open batch (the array is zero otherwise)
         HIP_TRY(hipMemsetAsync(c->d_tally.get(), 0, sizeof(unsigned long long) * c->gt.rows, c->stream.get()));
     c->chunks_used = 0;
@@ -129,6 +129,8 @@ static int zero_state(nps_ctx *c) {
     c->res_pending = false;  // unflushed stats of a resident run are dropped, never copied
     c->res_index.clear();
     c->res_host_stats.clear();
+    c->groups = nullptr;
+    c->plain_rows = false;
     return NPS_OK;
 }
 
@@ -245,6 +247,13 @@ int check_usable(nps_ctx *c) {
     return NPS_OK;
 }
 
+// A grouped context (nps_score_cohort_def_groups) takes grouped calls only until nps_reset
+int check_ungrouped(const nps_ctx *c, const char *what) {
+    if (c->groups)
+        return fail(NPS_E_STATE, "%s on a context that scores sample groups (nps_score_cohort_def_groups); nps_reset first", what);
+    return NPS_OK;
+}
+
 // run the open batch: params -> accumulate; then collect its stats
 int run_batch(nps_ctx *c) {
     if (c->res_pending && !c->pending.empty()) {  // keep stats in push order
@@ -335,6 +344,7 @@ static void commit_data_row(nps_ctx *c, OpenBatch &b, uint32_t slot) {
     memset(&p.host, 0, sizeof p.host);
     c->pending.push_back(p);
     b.rows = slot + 1;
+    c->plain_rows = true;
 }
 
 static int ensure_ds(nps_ctx *c);
@@ -377,6 +387,7 @@ extern "C" int nps_pl_likelihoods(double *out256) {
 extern "C" int nps_push_pl(nps_ctx *c, const void *pl, int elem_bytes, int n_alleles, int eaidx, int ref_is_effect,
                            double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_pl")) return grc;
     if (int arc = check_raw_pl(elem_bytes, n_alleles, eaidx)) return arc;
     if (c->n && !pl) return fail(NPS_E_INVAL, "pl is NULL");
     HIP_TRY(hipSetDevice(c->device));
@@ -403,6 +414,7 @@ extern "C" int nps_push_pl(nps_ctx *c, const void *pl, int elem_bytes, int n_all
 static int push_gt_typed(nps_ctx *c, const void *gts, int elem_bytes, int ploidy, int eaidx,
                          int ref_is_effect, double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_gt")) return grc;
     if (c->n && !gts) return fail(NPS_E_INVAL, "gts is NULL");
     if (int arc = check_raw_gt(elem_bytes, ploidy, eaidx, 8)) return arc;
     HIP_TRY(hipSetDevice(c->device));
@@ -467,6 +479,7 @@ static int push_2bit(nps_ctx *c, const void *row, int bed_mode, int ref_is_effec
 extern "C" int nps_push_packed(nps_ctx *c, const uint32_t *row, int ref_is_effect, double beta,
                                double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_packed")) return grc;
     if (c->n && !row) return fail(NPS_E_INVAL, "row is NULL");
     return push_2bit(c, row, -1, ref_is_effect, beta, eaf);
 }
@@ -474,6 +487,7 @@ extern "C" int nps_push_packed(nps_ctx *c, const uint32_t *row, int ref_is_effec
 extern "C" int nps_push_bed(nps_ctx *c, const uint8_t *bed_row, int effect_is_a1, int ref_is_effect,
                             double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_bed")) return grc;
     if (c->n && !bed_row) return fail(NPS_E_INVAL, "bed_row is NULL");
     if (effect_is_a1 < 0 || effect_is_a1 > NPS_MAP_PGEN_REF) return fail(NPS_E_INVAL, "bad code map %d", effect_is_a1);
     return push_2bit(c, bed_row, effect_is_a1, ref_is_effect, beta, eaf);
@@ -505,6 +519,7 @@ static int ensure_ds(nps_ctx *c) {
 
 extern "C" int nps_push_ds(nps_ctx *c, const float *ds, int ref_is_effect, double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_ds")) return grc;
     if (c->n && !ds) return fail(NPS_E_INVAL, "ds is NULL");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_ds(c);
@@ -526,6 +541,7 @@ extern "C" int nps_push_ds(nps_ctx *c, const float *ds, int ref_is_effect, doubl
 
 extern "C" int nps_push_locus(nps_ctx *c, int kind, int ref_is_effect, double beta, double eaf) {
     if (int urc = check_usable(c)) return urc;
+    if (int grc = check_ungrouped(c, "nps_push_locus")) return grc;
     if (kind != NPS_ROW_UNCOVERED && kind != NPS_ROW_ABSENT && kind != NPS_ROW_FILTERED)
         return fail(NPS_E_INVAL, "kind %d is not a no-data row kind", kind);
     PendingRow p;
@@ -533,12 +549,14 @@ extern "C" int nps_push_locus(nps_ctx *c, int kind, int ref_is_effect, double be
     p.is_ds = 0;
     host_locus_row(c, kind, ref_is_effect, beta, eaf, &p.host);
     c->pending.push_back(p);
+    c->plain_rows = true;
     return NPS_OK;
 }
 
 // the device's result block (used rows, status bits) -> pinned host copy; the caller synchronises
-static int fetch_result(nps_ctx *c) {
-    HIP_TRY(hipMemcpyAsync(c->h_result, c->d_nloci.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+// (words: 3, or kResultWords with the groups' counts)
+static int fetch_result(nps_ctx *c, size_t words = 3) {
+    HIP_TRY(hipMemcpyAsync(c->h_result, c->d_nloci.get(), words * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            c->stream.get()));
     return NPS_OK;
 }
@@ -552,9 +570,9 @@ static int check_status(nps_ctx *c) {
     return NPS_OK;
 }
 
-extern "C" int nps_flush(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size_t *n_out) {
-    int rc = check_usable(c);
-    if (rc) return rc;
+// nps_flush and nps_flush_groups: the rows -- of a grouped context the (row, group) entries -- completed and copied out
+static int flush_common(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size_t *n_out) {
+    int rc = NPS_OK;
     HIP_TRY(hipSetDevice(c->device));
     if (stats_out) rc = materialize_resident_stats(c);
     if (rc) return rc;
@@ -575,6 +593,20 @@ extern "C" int nps_flush(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size
     }
     if (n_out) *n_out = n;
     return NPS_OK;
+}
+
+extern "C" int nps_flush(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size_t *n_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    if (stats_out && (rc = check_ungrouped(c, "nps_flush with stats_out"))) return rc;
+    return flush_common(c, stats_out, cap, n_out);
+}
+
+extern "C" int nps_flush_groups(nps_ctx *c, nps_locus_stat *stats_out, size_t cap, size_t *n_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    if (!c->groups) return fail(NPS_E_STATE, "nps_flush_groups on a context that has taken no grouped call since its last reset");
+    return flush_common(c, stats_out, cap, n_out);
 }
 
 // nimpress.nim:643-649 on the device, one enqueue and ONE synchronisation: the finish kernel reads
@@ -603,6 +635,7 @@ static int finish_common(nps_ctx *c, double offset, double *d_dst, double *h_sco
 extern "C" int nps_finish(nps_ctx *c, double offset, double *scores_out, uint64_t *nloci_out) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_finish"))) return rc;
     if (c->n && !scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return finish_common(c, offset, c->d_scores.get(), scores_out, nloci_out);
@@ -612,6 +645,7 @@ extern "C" int nps_finish_device(nps_ctx *c, double offset, double *d_scores_out
                                  uint64_t *nloci_out) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_finish_device"))) return rc;
     if (c->n && !d_scores_out) return fail(NPS_E_INVAL, "d_scores_out is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return finish_common(c, offset, d_scores_out, nullptr, nloci_out);
@@ -653,6 +687,7 @@ static int finish_subset_common(nps_ctx *c, const nps_sampleset *s, double offse
 extern "C" int nps_finish_subset(nps_ctx *c, const nps_sampleset *s, double offset, double *scores_out, uint64_t *nloci_out) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_finish_subset"))) return rc;
     rc = check_sampleset(c, s);
     if (rc) return rc;
     if (!scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
@@ -665,6 +700,7 @@ extern "C" int nps_finish_subset_device(nps_ctx *c, const nps_sampleset *s, doub
                                         uint64_t *nloci_out) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_finish_subset"))) return rc;
     rc = check_sampleset(c, s);
     if (rc) return rc;
     if (!d_scores_out) return fail(NPS_E_INVAL, "d_scores_out is NULL");
@@ -675,9 +711,60 @@ extern "C" int nps_finish_subset_device(nps_ctx *c, const nps_sampleset *s, doub
 extern "C" int nps_partial_device(nps_ctx *c, double *d_sums_out, uint64_t *nloci_out) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_partial_device"))) return rc;
     if (c->n && !d_sums_out) return fail(NPS_E_INVAL, "d_sums_out is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return finish_common(c, 0.0, d_sums_out, nullptr, nloci_out, false);
+}
+
+// nps_finish for every group of a grouped context: one enqueue and one synchronisation like finish_common, the groups' counts
+// of used rows in the same copy as the status block
+static int finish_groups_common(nps_ctx *c, const nps_samplegroups *g, double offset, double *d_dst, double *h_scores_out,
+                                uint64_t *nloci_out) {
+    {
+        ProfScope ps(c, P_REDUCE);
+        HIP_TRY(launch_groups_finish(c->stream.get(), c->d_part.get(), c->chunks_used, c->geom.part_chunk_stride, c->n, c->const_sum,
+                                     g->d_label.get(), c->d_nloci.get() + kGroupNloci, c->host_nloci, offset, d_dst));
+    }
+    int rc = fetch_result(c, kResultWords);
+    if (rc) return rc;
+    if (h_scores_out)
+        HIP_TRY(hipMemcpyAsync(h_scores_out, d_dst, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    rc = check_status(c);
+    if (rc) return rc;
+    if (nloci_out)
+        for (int k = 0; k < g->n_groups; ++k) nloci_out[k] = c->host_nloci + c->h_result[kGroupNloci + k];
+    return NPS_OK;
+}
+
+// the groups object of a grouped context's calls: the one its first grouped call named
+static int check_groups_of(const nps_ctx *c, const nps_samplegroups *g, const char *what) {
+    if (!g) return fail(NPS_E_INVAL, "groups is NULL");
+    if (!c->groups) return fail(NPS_E_STATE, "%s on a context that has taken no grouped call since its last reset", what);
+    if (g != c->groups) return fail(NPS_E_INVAL, "%s: not the groups object this context scores (one per context until nps_reset)", what);
+    return NPS_OK;
+}
+
+extern "C" int nps_finish_groups(nps_ctx *c, const nps_samplegroups *g, double offset, double *scores_out, uint64_t *nloci_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    rc = check_groups_of(c, g, "nps_finish_groups");
+    if (rc) return rc;
+    if (!scores_out) return fail(NPS_E_INVAL, "scores_out is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return finish_groups_common(c, g, offset, c->d_scores.get(), scores_out, nloci_out);
+}
+
+extern "C" int nps_finish_groups_device(nps_ctx *c, const nps_samplegroups *g, double offset, double *d_scores_out,
+                                        uint64_t *nloci_out) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    rc = check_groups_of(c, g, "nps_finish_groups_device");
+    if (rc) return rc;
+    if (!d_scores_out) return fail(NPS_E_INVAL, "d_scores_out is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return finish_groups_common(c, g, offset, d_scores_out, nullptr, nloci_out);
 }
 
 extern "C" int nps_normalize_device(nps_ctx *c, double *d_sums, uint64_t nloci, double offset) {
@@ -696,19 +783,23 @@ extern "C" int nps_normalize_device(nps_ctx *c, double *d_sums, uint64_t nloci, 
 // stats of the last resident run (nps_resident.hip) stay on the device until somebody asks for them
 int materialize_resident_stats(nps_ctx *c) {
     if (!c->res_pending) return NPS_OK;
-    std::vector<nps_locus_stat> dev(c->res_m);
+    // (a grouped run: G entries per row, group-minor -- a row without data repeats its one statistic for every group)
+    const size_t G = c->groups ? (size_t)c->groups->n_groups : 1;
+    const nps_locus_stat *src = c->groups ? c->d_grp_stats.get() : c->d_rstats.get();
+    std::vector<nps_locus_stat> dev(c->res_m * G);
     if (c->res_m) {
-        HIP_TRY(hipMemcpyAsync(dev.data(), c->d_rstats.get(), sizeof(nps_locus_stat) * c->res_m,
+        HIP_TRY(hipMemcpyAsync(dev.data(), src, sizeof(nps_locus_stat) * c->res_m * G,
                                hipMemcpyDeviceToHost, c->stream.get()));
         HIP_TRY(hipStreamSynchronize(c->stream.get()));
     }
     size_t h = 0;
     for (size_t j = 0; j < c->res_index.size(); ++j) {
         if (c->res_index[j] < 0) {
-            c->ready.push_back(c->res_host_stats[h++]);
+            c->ready.insert(c->ready.end(), G, c->res_host_stats[h++]);
             continue;
         }
-        c->ready.push_back(dev[(size_t)c->res_index[j]]);
+        const nps_locus_stat *e = dev.data() + (size_t)c->res_index[j] * G;
+        c->ready.insert(c->ready.end(), e, e + G);
     }
     c->res_pending = false;
     c->res_index.clear();

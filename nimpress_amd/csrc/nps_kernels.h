@@ -399,4 +399,31 @@ hipError_t launch_mx_tally_masked(hipStream_t st, const MxPlan &plan, const void
 hipError_t launch_subset_gather(hipStream_t st, const double *d_scores, uint64_t n, const uint32_t *d_bits,
                                 const uint32_t *d_prefix, double *d_out);
 
+// ---- every group of a sample partition in two reads of a dosage cohort, NPS_FMT_DS32 / NPS_FMT_DS16 (nps_groups.hip; the
+// labels: nps_group_labels.h) ----
+struct GroupRowP {   // per row, what the grouped accumulation reads
+    double beta;
+    double cst;      // the locus constant of a group that has the row over --maxmis (the row's alone)
+    uint32_t modes;  // bits 2k, 2k + 1: group k's mode -- 0 dropped, 1 genotyped (imp[row][k] for missing samples), 2 cst
+    int32_t rie;     // effect allele is REF: dosage = 2 - DS
+};
+// d_label: one byte per sample, padded with 255 to a multiple of 64; d_present: one byte per 256 samples; d_tally:
+// [n_rows][n_groups], group k's pair with the bits of launch_ds_tally under the mask {label == k}.  elem_bytes 4: float32
+// rows; 2: NPS_FMT_DS16 rows.  stride_e: elements per row
+hipError_t launch_groups_tally(hipStream_t st, const void *d_ds, int elem_bytes, uint64_t stride_e, uint64_t n,
+                               const nps_row_desc *d_desc, uint64_t n_rows, const unsigned char *d_label,
+                               const unsigned char *d_present, int n_groups, DsTally *d_tally);
+// d_size: [n_groups] samples per group; d_imp: [n_rows][8]; d_stats: [n_rows][n_groups]; adds the rows used for group k to d_nloci[k]
+hipError_t launch_groups_params(hipStream_t st, const DsTally *d_tally, const nps_row_desc *d_desc, uint64_t n_rows, int n_groups,
+                                const unsigned long long *d_size, DevParams p, GroupRowP *d_rowp, double *d_imp,
+                                nps_locus_stat *d_stats, unsigned long long *d_nloci);
+// grid, row chunks and partial planes of launch_ds_accumulate
+hipError_t launch_groups_accumulate(hipStream_t st, const void *d_ds, int elem_bytes, uint64_t stride_e, uint64_t n,
+                                    const unsigned char *d_label, const GroupRowP *d_rowp, const double *d_imp, uint64_t n_rows,
+                                    double *d_part, uint32_t n_chunks, uint64_t part_chunk_stride);
+// launch_finish with nloci = host_nloci + d_nloci[label[i]]; a sample without a group gets NaN
+hipError_t launch_groups_finish(hipStream_t st, const double *d_part, uint32_t n_chunks, uint64_t part_chunk_stride,
+                                uint64_t n_samples, double const_sum, const unsigned char *d_label,
+                                const unsigned long long *d_nloci, uint64_t host_nloci, double offset, double *d_scores);
+
 }  // namespace nps

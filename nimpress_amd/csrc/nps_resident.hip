@@ -1,10 +1,11 @@
 // nps_resident.hip -- scoring a resident cohort (one of four units, nps_engine.h): the score definition nps_scoredef, the
-// sample set nps_sampleset, and nps_score_cohort[_def[_subset]] with its three families of formats.  Host-side
-// orchestration only; which fixed-point scales a definition gets is decided in nps_scale.h.
+// sample set nps_sampleset, the sample groups nps_samplegroups, and nps_score_cohort[_def[_subset | _groups]] with its three
+// families of formats.  Host-side orchestration only; which fixed-point scales a definition gets is decided in nps_scale.h.
 #include <cstdio>
 #include <new>
 
 #include "nps_engine.h"
+#include "nps_group_labels.h"
 #include "nps_scale.h"
 #include "nps_subset_mask.h"
 
@@ -310,15 +311,17 @@ static int score_run_mx(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
 
 // NPS_FMT_DS32 / NPS_FMT_DS16: the single-read kernel (plan.ok), else -- float32 rows only -- tally, params, accumulate
 // (set: a subset run -- always the three launches, the tally counted under the set's mask and the decisions with N = kept
-// samples; the accumulation is the cohort's)
+// samples; the accumulation is the cohort's.  grp: a grouped run -- the three launches in their grouped form (nps_groups.hip),
+// a tally and a decision per group, either dosage format)
 static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
-                        int mode, const FusedPlan &plan, uint64_t n_tally, const nps_sampleset *set) {
+                        int mode, const FusedPlan &plan, uint64_t n_tally, const nps_sampleset *set,
+                        const nps_samplegroups *grp = nullptr) {
     const uint64_t m = def->m;
     const uint64_t n_decide = set ? set->n_kept : c->n;
     const bool is_ds16 = co->format == NPS_FMT_DS16;
     const uint64_t stride_f = co->stride_bytes / 4;  // (NPS_FMT_DS32 only below the fused branch)
     const float *ds = (const float *)((const char *)co->d_data.get() + cohort_row0 * co->stride_bytes);
-    if (plan.ok && c->n && !set) {
+    if (plan.ok && c->n && !set && !grp) {
         bool ran = false;
         int rc = single_read(c, guard, plan, n_tally, "fused DS", mode == NPS_MODE_AUTO && !is_ds16, [&]() {
             return launch_ds_fused(c->stream.get(), plan, ds, co->stride_bytes, is_ds16 ? 2 : 4, c->n, m, def->d_desc.get(),
@@ -327,7 +330,9 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
         }, &ran);
         if (rc || ran) return rc;
     }
-    if (is_ds16) return fail(NPS_E_UNSUPPORTED, "NPS_FMT_DS16 cohorts are scored by the single-read kernel only");
+    if (is_ds16 && !grp) return fail(NPS_E_UNSUPPORTED, "NPS_FMT_DS16 cohorts are scored by the single-read kernel only");
+    const int elem_bytes = is_ds16 ? 2 : 4;                   // (the grouped launches take rows of either format:
+    const uint64_t stride_e = co->stride_bytes / elem_bytes;  //  their elements, and their stride in elements)
     // launches of >= 2048 rows keep every CU busy in both kernels (one workgroup per row in the
     // tally; samples x row chunks in the accumulation)
     uint64_t block_rows = env_u64("NPS_BLOCK_ROWS", 0);
@@ -338,6 +343,29 @@ static int score_run_ds(nps_ctx *c, RunGuard &guard, const nps_cohort *co, uint6
     // (more than one block: tests/test_gpu_seams.py seam_ds32_two_pass_blocks)
     for (uint64_t r0 = 0; r0 < m; r0 += block_rows) {
         const uint64_t k = std::min(block_rows, m - r0);
+        if (grp) {
+            const void *rows = (const char *)ds + r0 * co->stride_bytes;
+            const int G = grp->n_groups;
+            {
+                ProfScope ps(c, P_TALLY);
+                HIP_TRY(launch_groups_tally(c->stream.get(), rows, elem_bytes, stride_e, c->n, def->d_desc.get() + r0, k,
+                                            grp->d_label.get(), grp->d_present.get(), G, c->d_grp_tally.get() + r0 * G));
+            }
+            {
+                ProfScope ps(c, P_PARAMS);
+                HIP_TRY(launch_groups_params(c->stream.get(), c->d_grp_tally.get() + r0 * G, def->d_desc.get() + r0, k, G,
+                                             grp->d_size.get(), dev_params(c->params), c->d_grp_rowp.get() + r0,
+                                             c->d_grp_imp.get() + r0 * 8, c->d_grp_stats.get() + r0 * G,
+                                             c->d_nloci.get() + kGroupNloci));
+            }
+            {
+                ProfScope ps(c, P_ACCUM);
+                HIP_TRY(launch_groups_accumulate(c->stream.get(), rows, elem_bytes, stride_e, c->n, grp->d_label.get(),
+                                                 c->d_grp_rowp.get() + r0, c->d_grp_imp.get() + r0 * 8, k, c->d_part.get(),
+                                                 c->n_chunks, c->geom.part_chunk_stride));
+            }
+            continue;
+        }
         {
             ProfScope ps(c, P_TALLY);
             HIP_TRY(launch_ds_tally(c->stream.get(), ds + r0 * stride_f, stride_f, c->n, def->d_desc.get() + r0, k,
@@ -454,6 +482,20 @@ static int fused_plan_for_run(nps_ctx *c, const nps_cohort *co, uint64_t m, int 
     return NPS_OK;
 }
 
+// a run's launches are queued: its rows without genotype data are applied, and its statistics wait for nps_flush
+static void commit_run(nps_ctx *c, const nps_scoredef *def) {
+    c->res_host_stats.clear();
+    c->res_host_stats.reserve(def->host_rows.size());
+    for (const nps_row_desc &r : def->host_rows) {  // host decided; nimpress.nim:526-558
+        nps_locus_stat st;
+        host_locus_row(c, r.kind, r.ref_is_effect, r.beta, r.eaf, &st);
+        c->res_host_stats.push_back(st);
+    }
+    c->res_index = def->data_index;
+    c->res_m = def->m;
+    c->res_pending = true;
+}
+
 // Everything that can be refused is checked BEFORE the context changes: a call that returns an error
 // from its validation leaves the context exactly as it was, so it can be repeated (e.g. in another
 // mode).  The rows without genotype data are applied, and the run is registered for nps_flush, only
@@ -464,6 +506,7 @@ static int score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t cohort_ro
                             const nps_sampleset *set) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, set ? "nps_score_cohort_def_subset" : "nps_score_cohort_def"))) return rc;
     if (!co || !def) return fail(NPS_E_INVAL, "cohort or scoredef is NULL");
     if (co->device != c->device || def->device != c->device)
         return fail(NPS_E_INVAL, "cohort / scoredef / context on different devices");
@@ -533,16 +576,8 @@ static int score_cohort_def(nps_ctx *c, const nps_cohort *co, uint64_t cohort_ro
 
     // the run is registered only after its launches are queued (commit below)
     auto commit = [&]() {
-        c->res_host_stats.clear();
-        c->res_host_stats.reserve(def->host_rows.size());
-        for (const nps_row_desc &r : def->host_rows) {  // host decided; nimpress.nim:526-558
-            nps_locus_stat st;
-            host_locus_row(c, r.kind, r.ref_is_effect, r.beta, r.eaf, &st);
-            c->res_host_stats.push_back(st);
-        }
-        c->res_index = def->data_index;
-        c->res_m = m;
-        c->res_pending = true;
+        commit_run(c, def);
+        c->plain_rows = true;
     };
     if (m == 0) {
         commit();
@@ -638,6 +673,7 @@ extern "C" int nps_score_cohort_def_subset(nps_ctx *c, const nps_cohort *co, uin
                                            const nps_sampleset *s) {
     int rc = check_usable(c);
     if (rc) return rc;
+    if ((rc = check_ungrouped(c, "nps_score_cohort_def_subset"))) return rc;
     if (!co || !def) return fail(NPS_E_INVAL, "cohort or scoredef is NULL");
     rc = check_sampleset(c, s);
     if (rc) return rc;
@@ -657,9 +693,107 @@ extern "C" int nps_score_cohort_def_subset(nps_ctx *c, const nps_cohort *co, uin
     return score_cohort_def(c, co, cohort_row0, def, NPS_MODE_TWOPASS, s);
 }
 
+// ------------------------------------------------------------------------------------------
+// every group of a sample partition in one pass (the kernels: nps_groups.hip; the labels: nps_group_labels.h)
+extern "C" int nps_samplegroups_create(nps_samplegroups **out, int device, uint64_t n_samples, const uint8_t *label, int n_groups) {
+    if (!out) return fail(NPS_E_INVAL, "out is NULL");
+    *out = nullptr;
+    if (!label) return fail(NPS_E_INVAL, "label is NULL");
+    if (n_samples == 0) return fail(NPS_E_INVAL, "sample groups of no samples");
+    if (n_groups < 1 || n_groups > NPS_GROUPS_MAX) return fail(NPS_E_INVAL, "n_groups %d outside 1 .. %d", n_groups, NPS_GROUPS_MAX);
+    if (n_samples > 0x7fffffffull) return fail(NPS_E_UNSUPPORTED, "n_samples %llu exceeds 2^31-1", (unsigned long long)n_samples);
+    const GroupLabelCheck chk = group_labels_check(label, n_samples, n_groups);
+    if (chk.error == kGroupLabelBad)
+        return fail(NPS_E_INVAL, "sample %llu has label %d: neither a group 0 .. %d nor NPS_GROUP_NONE", (unsigned long long)chk.sample,
+                    (int)label[chk.sample], n_groups - 1);
+    if (chk.error == kGroupLabelsAllNone)
+        return fail(NPS_E_INVAL, "every one of the %llu labels is NPS_GROUP_NONE: no sample in any group", (unsigned long long)n_samples);
+    if (chk.error == kGroupLabelEmpty) return fail(NPS_E_INVAL, "group %d has no sample", chk.group);
+    int rc = select_device(device);
+    if (rc) return rc;
+    const GroupLabels gl = group_labels(label, n_samples, n_groups);
+    std::unique_ptr<nps_samplegroups> owner(new (std::nothrow) nps_samplegroups);
+    nps_samplegroups *g = owner.get();
+    if (!g) return fail(NPS_E_NOMEM, "out of host memory");
+    g->device = device;
+    g->n_samples = n_samples;
+    g->n_groups = n_groups;
+    unsigned long long size[kGroupsMax];
+    for (int k = 0; k < kGroupsMax; ++k) size[k] = g->size[k] = gl.size[k];
+    HIP_TRY(g->d_label.alloc(gl.label.size()));
+    HIP_TRY(g->d_present.alloc(gl.present.size()));
+    HIP_TRY(g->d_size.alloc(kGroupsMax));
+    HIP_TRY(hipMemcpy(g->d_label.get(), gl.label.data(), gl.label.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->d_present.get(), gl.present.data(), gl.present.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->d_size.get(), size, sizeof size, hipMemcpyHostToDevice));
+    *out = owner.release();
+    return NPS_OK;
+}
+extern "C" int nps_samplegroups_n_groups(const nps_samplegroups *g) { return g ? g->n_groups : 0; }
+extern "C" uint64_t nps_samplegroups_n_samples(const nps_samplegroups *g) { return g ? g->n_samples : 0; }
+extern "C" uint64_t nps_samplegroups_size(const nps_samplegroups *g, int group) {
+    return g && group >= 0 && group < g->n_groups ? g->size[group] : 0;
+}
+extern "C" void nps_samplegroups_destroy(nps_samplegroups *g) { delete g; }
+
+// Everything is refused before the context changes, as for nps_score_cohort_def; the launches are score_run_ds's three per
+// block of rows in their grouped form.  The context is grouped, with this groups object, once the first run is committed.
+extern "C" int nps_score_cohort_def_groups(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0, const nps_scoredef *def,
+                                           const nps_samplegroups *g) {
+    int rc = check_usable(c);
+    if (rc) return rc;
+    if (!co || !def) return fail(NPS_E_INVAL, "cohort or scoredef is NULL");
+    if (!g) return fail(NPS_E_INVAL, "groups is NULL");
+    if (co->device != c->device || def->device != c->device)
+        return fail(NPS_E_INVAL, "cohort / scoredef / context on different devices");
+    if (g->device != c->device) return fail(NPS_E_INVAL, "sample groups and context are on different devices");
+    if (g->n_samples != c->n)
+        return fail(NPS_E_INVAL, "sample groups have %llu samples, context %llu", (unsigned long long)g->n_samples,
+                    (unsigned long long)c->n);
+    if (g->n_samples != co->n_samples)
+        return fail(NPS_E_INVAL, "sample groups have %llu samples, cohort %llu", (unsigned long long)g->n_samples,
+                    (unsigned long long)co->n_samples);
+    if (co->format != NPS_FMT_DS32 && co->format != NPS_FMT_DS16)
+        return fail(NPS_E_UNSUPPORTED, "sample groups are scored on NPS_FMT_DS32 and NPS_FMT_DS16 cohorts; this one is %s",
+                    format_name(co->format));
+    if (c->groups && c->groups != g)
+        return fail(NPS_E_INVAL, "this context scores another groups object (one per context until nps_reset)");
+    if (!c->groups && c->plain_rows)
+        return fail(NPS_E_STATE, "a grouped call on a context that holds ungrouped rows; nps_reset first");
+    const uint64_t m = def->m;
+    rc = check_range(co, cohort_row0, m);
+    if (rc) return rc;
+    rc = cohort_quiesce(co);  // rows pushed into the cohort (nps_cohort_push_*) are complete
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = materialize_resident_stats(c);  // (an earlier grouped run's entries leave d_grp_stats)
+    if (rc) return rc;
+    auto commit = [&]() {
+        commit_run(c, def);
+        c->groups = g;
+    };
+    if (m == 0) {
+        commit();
+        return NPS_OK;
+    }
+    // buffers (a failed allocation leaves the context usable: nothing has been queued yet)
+    const uint64_t G = (uint64_t)g->n_groups;
+    HIP_TRY(c->d_grp_tally.ensure(m * G, c->stream.get()));
+    HIP_TRY(c->d_grp_rowp.ensure(m, c->stream.get()));
+    HIP_TRY(c->d_grp_imp.ensure(m * 8, c->stream.get()));
+    HIP_TRY(c->d_grp_stats.ensure(m * G, c->stream.get()));
+    RunGuard guard{c};
+    rc = score_run_ds(c, guard, co, cohort_row0, def, NPS_MODE_TWOPASS, FusedPlan{}, 0, nullptr, g);
+    if (rc) return rc;
+    commit();
+    guard.ok = true;
+    return NPS_OK;
+}
+
 extern "C" int nps_score_cohort(nps_ctx *c, const nps_cohort *co, uint64_t cohort_row0,
                                 const nps_row_desc *rows, uint64_t n_desc, int mode) {
     if (!c || !co) return fail(NPS_E_INVAL, "ctx or cohort is NULL");
+    if (int grc = check_ungrouped(c, "nps_score_cohort")) return grc;
     nps_scoredef *def = nullptr;
     int rc = nps_scoredef_create(&def, c->device, rows, n_desc);
     if (rc) return rc;
